@@ -2,7 +2,18 @@
 """Benchmark: rendered rays/s per mapping iteration (BASELINE.json metric) on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload room0|map|fwd|map-points] [--rays R]
-                  [--global-batch B] [--precision P] [--graph] [--no-extras] [--no-cpu-baseline]
+                  [--global-batch B] [--precision P] [--graph] [--dump-outputs DIR]
+                  [--full [--no-extras] [--no-cpu-baseline] [--no-gather]]
+
+A plain run sets up, runs W untimed and K timed steps of the workload and prints the result line
+(`value`, `ms_per_step`, and the figures the timed steps' own kernel timings give).  `--full` adds
+every measurement that takes runs of its own, after the timed region: the eager pass behind the room0
+kernel rooflines, the oracle's CPU rates and parity, the extra workloads below and the gather line
+(`--no-extras`, `--no-cpu-baseline` and `--no-gather` leave parts of a `--full` run out).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32): the loss
+and the decoder's flat parameter and gradient buffers of a mapping workload, depth / uncertainty /
+colour of `fwd`; an array above 16 MB is stored as a fixed seeded sample of its elements.  The inputs
+are the same from run to run (fixed seeds), so two builds can be compared output for output.
 
 Workload `room0` (default; the metric's own iteration, configs/Replica/replica.yaml:21-22 +
 configs/pointNeRF_slam.yaml): ONE room0 Mapper iteration of src/Mapper.py:507-662 at its real size --
@@ -15,7 +26,7 @@ Workload `map` ("S-map"): the same iteration over R rays per GPU
 samples.  Decoder arithmetic: f16x3 by default -- fp32-class end to end (every forward and backward GEMM
 on 22-bit split operands with fp32 accumulation, include/pnr.h); `--precision fp32` runs fp32 MFMA.
 
-Extra keys of the default line (measured after the timed region, never part of `value`):
+Extra keys of the default workload's `--full` line (measured after the timed region, never part of `value`):
   smap            S-map at 307,200 rays per GPU with its MLP rooflines and the oracle's CPU rate
                   (`smap_value` repeats its rays/s at the top level)
   sfwd            the north-star S-fwd batch (640x480 x 64 samples, forward) with its own roofline
@@ -26,7 +37,7 @@ Extra keys of the default line (measured after the timed region, never part of `
   fp32            the S-map step with fp32-MFMA decoder arithmetic
   gather_roofline the neural-point gather (A15) on its HBM roofline
   room0_iter_fp32 the headline's room0 iteration (graph replay) in strict fp32 MFMA (config C2's precision)
-N>1 lines (one rank per GPU, RCCL) carry `smap` (weak: 307,200 rays per GPU), `fixed_global_batch`
+N>1 `--full` lines (one rank per GPU, RCCL) carry `smap` (weak: 307,200 rays per GPU), `fixed_global_batch`
 (ONE 307,200-ray batch split over the ranks: strong scaling), `sfwd` (weak: 640x480 x 64
 samples per GPU) and `sfwd_fixed_global` (one 640x480 batch split over the ranks), rank 0's
 `gather_roofline`, and `distributed` (the backend and world size the ranks saw).
@@ -389,6 +400,28 @@ def timed(step, steps, warmup, ddp, lib):
     return el, kt
 
 
+DUMP_MAX_ELEMS = 4 << 20           # per dumped array: 16 MB of float32 (at most 3 arrays per workload)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each tensor of `arrays` (name -> tensor) as path/<name>.npy, float32.  An
+    array above DUMP_MAX_ELEMS elements is stored as a sample of its flattened elements at fixed
+    indices (numpy default_rng(0), sorted), the same in every run."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().reshape(-1) if t.dim() == 0 else t.detach()
+        if a.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.numel(), DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(path, name + '.npy'), a.float().cpu().numpy())
+
+
+def map_outputs(mstep, loss):
+    """What a caller of a mapping step holds after it: the loss, and the flat buffer of the updated
+    parameters (decoder, then fc_c and point features with neural points) with its gradient."""
+    return {'loss': loss, 'params': mstep.flat.data, 'grads': mstep.flat.grad}
+
+
 def kernel_roofline(kt, prec, el_s, traffic_units=True, fc=False, workload=None):
     """Roofline of the dominant hand-written kernel of the step -- the one with the most device time
     among the fused forward, the delta chain and the grouped weight-gradient launch -- per launch.
@@ -519,11 +552,11 @@ def map_step_fn(pnr, renderer, dec, cfg, ro, rd, gt, col, dev, ddp=None, points=
         def step():  # the same iteration, replayed; a fresh regulation jitter drawn per step, in place
             # into the graph's static input (the rays already sit in its other inputs: no copies)
             torch.rand((n, ns), device=dev, out=mgraph.inputs[4])
-            mgraph(*mgraph.inputs)
-        return step
-
-    def step():
-        mstep(ro, rd, gt, col, torch.rand((n, ns), device=dev))
+            step.loss = mgraph(*mgraph.inputs)
+    else:
+        def step():
+            step.loss = mstep(ro, rd, gt, col, torch.rand((n, ns), device=dev))
+    step.mstep = mstep   # for --dump-outputs: the last step's loss and the step's parameter buffers
     return step
 
 
@@ -662,12 +695,14 @@ def room0_window(pnr, params, bound, dev):
 
 
 def room0_extra(pnr, params, bound, pose, dev, ddp, lib, steps=100, warmup=5, cpu=True, graph=True, rank=0,
-                prec='f16x3'):
+                prec='f16x3', full=True, dump=None):
     """The metric's own workload: ONE room0 Mapper iteration (src/Mapper.py:507-662) at its real size,
     1,000 rays over the 5-frame window (200 per frame) of the room0 camera, gt = the decoder's own
     rendered depth / colour.  Timed per iteration: the window batch (pnr_window_sample: pixels, jitter
     and far clamp drawn on the device in one launch, src/Mapper.py:553-606), render (32 + 12 samples) + regulation (32) + fused L1 losses + backward +
-    Adam, all replayed from one captured HIP graph (pnr.MapGraph(batch_fn=pnr.mapping.WindowSampler))."""
+    Adam, all replayed from one captured HIP graph (pnr.MapGraph(batch_fn=pnr.mapping.WindowSampler)).
+    `full` adds the eager pass behind the kernel rooflines and (with `cpu`) the oracle's CPU rate;
+    `dump` = the --dump-outputs directory (rank 0 writes the last timed step's outputs there)."""
     from pnr.mapping import MapGraph, MapStep, WindowSampler
     slam, frames = room0_window(pnr, params, bound, dev)
     cfg = pnr.ROOM0_CFG
@@ -686,13 +721,12 @@ def room0_extra(pnr, params, bound, pose, dev, ddp, lib, steps=100, warmup=5, cp
         step = mg
     else:
         def step():
-            mstep(*sampler())
+            step.loss = mstep(*sampler())
     el, _ = timed(step, steps, warmup, ddp, lib)
     n = per * ROOM0_WINDOW
     rate = n * steps / el
-    # the same iteration launched eagerly, for the live per-kernel times (hipEvents around each launch;
-    # a graph replay has no per-launch host hook): the MLP kernels' rooflines at this batch size
-    el_e, kt = timed(lambda: mstep(*sampler()), 20, 3, ddp, lib)
+    if dump and rank == 0:  # before the eager pass below trains the same decoder on
+        dump_outputs(dump, map_outputs(mstep, mg.loss if graph else step.loss))
     tf = MAP_FLOP_PER_RAY * rate / 1e12
     peak = ALGO_PEAK_TF['fp32' if prec == 'fp32' else 'f16x3']
     out = {'workload': 'room0 Mapper iteration: 1,000 rays = 5-frame window x 200 uniform pixels on the 680x1200 '
@@ -702,12 +736,18 @@ def room0_extra(pnr, params, bound, pose, dev, ddp, lib, steps=100, warmup=5, cp
            'graph': graph, 'iters': steps, 'achieved_tflops': round(tf, 2), 'frac_of_split_peak': round(tf / peak, 4),
            'flop_basis': '115.29 MFLOP per ray per mapping iteration (SURVEY.md 8(d)); peak '
                          + ('157.3 TF (fp32 MFMA)' if prec == 'fp32' else '833 TF (f16 MFMA / 3)'),
-           'decoder_precision': prec, 'dtype': DTYPE[prec],
-           'eager_ms_per_iter': round(el_e / 20 * 1e3, 4),
-           'roofline': kernel_roofline(kt, prec, el_e, traffic_units=prec != 'fp32', workload='room0'),
-           'kernel_rooflines': kernel_table(kt, prec, el_e, 20) if prec != 'fp32' else None,
-           'kernel_profile': 'profiles/r06_room0_timeline.txt, profiles/r06_room0_kernel_stats.csv (rocprofv3 of '
-                             'the graph replay)'}
+           'decoder_precision': prec, 'dtype': DTYPE[prec]}
+    if not full:
+        return out
+    # the same iteration launched eagerly, for the live per-kernel times (hipEvents around each launch;
+    # a graph replay has no per-launch host hook): the MLP kernels' rooflines at this batch size
+    el_e, kt = timed(lambda: mstep(*sampler()), 20, 3, ddp, lib)
+    out.update({
+        'eager_ms_per_iter': round(el_e / 20 * 1e3, 4),
+        'roofline': kernel_roofline(kt, prec, el_e, traffic_units=prec != 'fp32', workload='room0'),
+        'kernel_rooflines': kernel_table(kt, prec, el_e, 20) if prec != 'fp32' else None,
+        'kernel_profile': 'profiles/r06_room0_timeline.txt, profiles/r06_room0_kernel_stats.csv (rocprofv3 of '
+                          'the graph replay)'})
     if cpu and prec != 'fp32':
         rays = sampler()[:4]
         cr = oracle_map_rate(bound, pose, params, n, rays=rays)
@@ -817,9 +857,15 @@ def main():
                     help='fixed global batch split over the ranks (strong scaling; SURVEY.md 8(e))')
     ap.add_argument('--graph', action='store_true',
                     help='replay the S-map iteration from a captured HIP graph (pnr.mapping.MapGraph)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-gather', action='store_true', help='skip the point-gather roofline line')
-    ap.add_argument('--no-extras', action='store_true', help='skip the extra workloads (smap, sfwd, faithful, ...)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure everything that takes runs of its own: the eager '
+                         'per-kernel pass, the oracle CPU baselines and parity, the extra workloads, the gather line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the oracle CPU legs')
+    ap.add_argument('--no-gather', action='store_true', help='with --full: skip the point-gather roofline line')
+    ap.add_argument('--no-extras', action='store_true',
+                    help='with --full: skip the extra workloads (smap, sfwd, faithful, ...)')
     ap.add_argument('--precision', default=None, help="decoder matmuls: f16x3 (default) | fp32 | bf16x3 | bf16")
     ap.add_argument('--feat-dtype', default='float32', choices=['float32', 'float16'],
                     help='neural-point feature storage (map-points workload and the gather line; C5: float16)')
@@ -830,6 +876,10 @@ def main():
         args.warmup = 5 if args.workload == 'room0' else 2
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if not args.full:  # a plain run measures its headline only
+        args.no_extras = args.no_cpu_baseline = args.no_gather = True
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args))
 
@@ -852,6 +902,7 @@ def main():
     rank, world, local = pdist.init()
     dev = torch.device('cuda', local % torch.cuda.device_count())
     torch.cuda.set_device(dev)
+    torch.manual_seed(rank)  # torch's draws (the regulation jitter of `map`) repeat from run to run
     dist_info = None
     if world > 1:
         import torch.distributed as tdist
@@ -869,7 +920,7 @@ def main():
 
     if args.workload == 'room0':  # the metric's own iteration (1,000 rays per GPU and iteration)
         e = room0_extra(pnr, params, bound, pose, dev, ddp, lib, steps=args.steps, warmup=args.warmup, cpu=cpu_ok,
-                        rank=rank)
+                        rank=rank, full=args.full, dump=args.dump_outputs)
         extras = {}
         if not args.no_extras:
             extras['smap'] = smap_run(pnr, plib, slam, params, bound, pose, dev, ddp, lib, rank, world, prec,
@@ -946,9 +997,12 @@ def main():
     else:
         def step():
             with torch.no_grad():
-                renderer.render_batch_ray({}, dec, rd, ro, dev, 'color', gt_depth=None)
+                step.out = renderer.render_batch_ray({}, dec, rd, ro, dev, 'color', gt_depth=None)
 
     el, kt = timed(step, args.steps, args.warmup, ddp, lib)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(('depth', 'uncertainty', 'color'), step.out))
+                     if args.workload == 'fwd' else map_outputs(step.mstep, step.loss))
     ms_per_step = el / args.steps * 1e3
     total = args.global_batch if strong else n * world
     value = total / (el / args.steps)

@@ -4,7 +4,7 @@
 # Steps (each under its own time limit; logs under gpurun_out/<TAG>_*, TAG from $PNR_TAG, default r04):
 #   tests       the whole -m gpu suite, then __graft_entry__.smoke()    (pytest failures stop the call)
 #   test:<k>    the -m gpu tests matching -k <k>
-#   bench       the default bench line (N=1, every extra and CPU baseline)
+#   bench       the default workload's --full bench line (N=1, every extra and CPU baseline)
 #   quick       the S-map line alone (no extras / CPU baseline / gather)
 #   faithful    the room0 Mapper iteration legs (graph replay) alone
 #   points      the neural-point S-map alone
@@ -47,14 +47,14 @@ for step in "$@"; do
         --timeout-method thread -p no:cacheprovider -k "$K"
       tail -3 "$L" ;;
     bench)
-      run 600 ${O}_bench.log python3 bench.py
+      run 600 ${O}_bench.log python3 bench.py --full
       tail -c 300 ${O}_bench.log; echo ;;
     quick)
       run 300 ${O}_quick.log python3 bench.py --workload map --steps 5 --warmup 2 --no-extras --no-cpu-baseline --no-gather
       grep -o '"value": [0-9.]*, "unit": "rays/s", "n_gpus": 1, "steps": [0-9]*, "warmup": [0-9]*, "ms_per_step": [0-9.]*' ${O}_quick.log
       grep -o '"frac": [0-9.]*' ${O}_quick.log | head -1 ;;
     faithful)
-      run 300 ${O}_faithful.log python3 bench.py --workload room0 --steps 100 --warmup 5 --no-cpu-baseline --no-extras
+      run 300 ${O}_faithful.log python3 bench.py --workload room0 --steps 100 --warmup 5 --full --no-cpu-baseline --no-extras
       tail -c 400 ${O}_faithful.log; echo ;;
     points)
       run 300 ${O}_points.log python3 bench.py --workload map-points --steps 3 --warmup 1 --no-cpu-baseline --no-gather
