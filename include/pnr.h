@@ -383,6 +383,44 @@ int pnr_map_step(const pnr_render_params* prm, const float* packed, const float*
                  float w_reg, double* loss, float* const* grads, void* workspace, size_t ws_bytes, void* bwd_ws,
                  size_t bwd_bytes, void* loss_ws, void* stream);
 
+/* ---- mesh extraction (src/utils/Mesher.py:349-574; additions to ABI 14) -------------------------
+ * Mesher.point_masks (:53-212) for one chunk of P float32 points (the caller splits by
+ * points_batch_size as the reference does: PNR_MASK_DEPTH_TEST's max_depth is a maximum over the
+ * points of ONE call).  w2c (K,4,4) float32 row-major = the host inverse of each keyframe's c2w.
+ *   PNR_MASK_POSES      get_mask_use_all_frames: frustum tests only (depth, max_depth NULL)
+ *   PNR_MASK_MAX_DEPTH  depth_test=False: both masks also need -cam.z < max_depth[k], a device
+ *                       float32 (K) the caller fills with 1.1 * max(depth_k)
+ *   PNR_MASK_DEPTH_TEST depth_test=True: depth (K,H,W) float32 is sampled at uv (F.grid_sample,
+ *                       bilinear, align_corners=True, zero padding); forecast needs -cam.z < the
+ *                       maximum sample of the call, seen needs |-cam.z - sample| < 2.4
+ * seen / forecast: P bytes each (0 / 1), forecast already without the seen points.  ws:
+ * pnr_point_masks_workspace_bytes(P, K, mode) bytes (0 for the first two modes).  Deterministic. */
+enum { PNR_MASK_POSES = 0, PNR_MASK_MAX_DEPTH = 1, PNR_MASK_DEPTH_TEST = 2 };
+size_t pnr_point_masks_workspace_bytes(int64_t P, int32_t K, int32_t mode);
+int pnr_point_masks(const float* points, int64_t P, const float* w2c, int32_t K, int32_t H, int32_t W, float fx,
+                    float fy, float cx, float cy, int32_t mode, const float* depth, const float* max_depth,
+                    uint8_t* seen, uint8_t* forecast, void* ws, size_t ws_bytes, void* stream);
+
+/* Marching cubes over a float32 volume of nx x ny x nz samples; sample (ix,iy,iz) is
+ * vol[ix*sx + iy*sy + iz*sz] (element strides, so the Mesher's (iy*nx + ix)*nz + iz grid order needs no
+ * transposed copy).  A corner is "below" when sample < level; an edge with exactly one below corner
+ * carries one vertex at origin + (i + t) * spacing, t = (level - a) / (b - a) in float64.  Each vertex
+ * is shared by the faces around it; vertices are ordered by owning grid point ((ix*ny + iy)*nz + iz,
+ * then x, y, z edge), faces by cell and case-table order; the winding is skimage's default.  No atomic
+ * decides a position: equal volumes give equal bits.  Two calls with the same arguments and workspace:
+ *   pnr_marching_cubes_count  fills ws and writes the vertex / face counts to two device int64
+ *   pnr_marching_cubes_emit   writes vertices (n_vertices,3) float64 and faces (n_faces,3) int32
+ * (the caller reads the counts and allocates in between; a volume without a crossing gives 0, 0).
+ * origin, spacing: HOST double[3].  nx*ny*nz <= pnr_marching_cubes_max_points(). */
+size_t pnr_marching_cubes_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+int64_t pnr_marching_cubes_max_points(void);
+int pnr_marching_cubes_count(const float* vol, int64_t nx, int64_t ny, int64_t nz, int64_t sx, int64_t sy,
+                             int64_t sz, double level, void* ws, size_t ws_bytes, int64_t* n_vertices,
+                             int64_t* n_faces, void* stream);
+int pnr_marching_cubes_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz, int64_t sx, int64_t sy,
+                            int64_t sz, double level, const double* origin, const double* spacing, const void* ws,
+                            size_t ws_bytes, double* vertices, int32_t* faces, void* stream);
+
 /* ---- diagnostics (not on the reference API) ----------------------------------------------- */
 /* Kernel timing: while enabled, every launch of the timed kernels is bracketed by hipEvents on
  * its own stream.  pnr_timing_read synchronises those events and returns, for `kernel`

@@ -68,6 +68,15 @@ int launch_fine_loss(const pnr_render_params&, const float*, const double*, cons
                      const float4*, const float4*, int64_t, const float*, const float*, float, float, const float*,
                      const float4*, float*, float*, float*, float*, float*, int, float*, int, float*, int, double*,
                      uint32_t*, double*, hipStream_t);
+int64_t point_masks_parts(int64_t P);
+int launch_point_masks(const float*, int64_t, const float*, int, int, int, float, float, float, float, int,
+                       const float*, const float*, uint8_t*, uint8_t*, float*, hipStream_t);
+int mc_max_tri();
+int64_t mc_workspace_bytes(int64_t n);
+int launch_mc_count(const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, double, void*, int64_t*,
+                    int64_t*, hipStream_t);
+int launch_mc_emit(const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, double, const double*,
+                   const double*, const void*, double*, int32_t*, hipStream_t);
 
 }  // namespace pnr
 
@@ -1330,6 +1339,65 @@ int pnr_adam_multi_dev_h(float* p, const float* g, int32_t n_seg, const int64_t*
 int pnr_step_advance(int32_t* step_count, void* stream) {
   if (!step_count) return PNR_E_ARG;
   return launch_step_advance(step_count, (hipStream_t)stream);
+}
+
+// ---- mesh extraction (mesh.hip) ---------------------------------------------------------------
+size_t pnr_point_masks_workspace_bytes(int64_t P, int32_t K, int32_t mode) {
+  if (P < 0 || P >= (1LL << 31) || K < 0 || mode < PNR_MASK_POSES || mode > PNR_MASK_DEPTH_TEST) return 0;
+  if (mode != PNR_MASK_DEPTH_TEST) return 0;
+  return (size_t)((int64_t)K * (1 + point_masks_parts(P))) * sizeof(float);
+}
+
+int pnr_point_masks(const float* points, int64_t P, const float* w2c, int32_t K, int32_t H, int32_t W, float fx,
+                    float fy, float cx, float cy, int32_t mode, const float* depth, const float* max_depth,
+                    uint8_t* seen, uint8_t* forecast, void* ws, size_t ws_bytes, void* stream) {
+  if (P < 0 || P >= (1LL << 31) || K < 0 || H <= 0 || W <= 0) return PNR_E_ARG;
+  if (mode < PNR_MASK_POSES || mode > PNR_MASK_DEPTH_TEST) return PNR_E_ARG;
+  if (P == 0) return PNR_OK;
+  if (!points || !seen || !forecast || (K > 0 && !w2c)) return PNR_E_ARG;
+  if (K == 0) {   // no keyframe: nothing is seen or forecast
+    if (hipMemsetAsync(seen, 0, (size_t)P, (hipStream_t)stream) != hipSuccess) return (int)hipGetLastError();
+    return hip_status(hipMemsetAsync(forecast, 0, (size_t)P, (hipStream_t)stream));
+  }
+  if (K > 0 && mode == PNR_MASK_MAX_DEPTH && !max_depth) return PNR_E_ARG;
+  if (K > 0 && mode == PNR_MASK_DEPTH_TEST) {
+    if (!depth || !ws || H < 2 || W < 2) return PNR_E_ARG;
+    if (ws_bytes < pnr_point_masks_workspace_bytes(P, K, mode)) return PNR_E_WORKSPACE;
+  }
+  return launch_point_masks(points, P, w2c, K, H, W, fx, fy, cx, cy, mode, depth, max_depth, seen, forecast,
+                            static_cast<float*>(ws), (hipStream_t)stream);
+}
+
+// faces hold int32 vertex indices and one launch covers every grid point: 3 vertices and
+// mc_max_tri() triangles per point must stay below 2^31
+int64_t pnr_marching_cubes_max_points(void) { return ((1LL << 31) - 1) / (mc_max_tri() > 3 ? mc_max_tri() : 3); }
+
+static bool mc_dims_ok(int64_t nx, int64_t ny, int64_t nz) {
+  const int64_t cap = pnr_marching_cubes_max_points();
+  if (nx < 1 || ny < 1 || nz < 1 || nx > cap || ny > cap || nz > cap) return false;
+  if (nx * ny > cap) return false;
+  return nx * ny * nz <= cap;
+}
+
+size_t pnr_marching_cubes_workspace_bytes(int64_t nx, int64_t ny, int64_t nz) {
+  return mc_dims_ok(nx, ny, nz) ? (size_t)mc_workspace_bytes(nx * ny * nz) : 0;
+}
+
+int pnr_marching_cubes_count(const float* vol, int64_t nx, int64_t ny, int64_t nz, int64_t sx, int64_t sy,
+                             int64_t sz, double level, void* ws, size_t ws_bytes, int64_t* n_vertices,
+                             int64_t* n_faces, void* stream) {
+  if (!mc_dims_ok(nx, ny, nz) || !vol || !ws || !n_vertices || !n_faces) return PNR_E_ARG;
+  if (ws_bytes < pnr_marching_cubes_workspace_bytes(nx, ny, nz)) return PNR_E_WORKSPACE;
+  return launch_mc_count(vol, nx, ny, nz, sx, sy, sz, level, ws, n_vertices, n_faces, (hipStream_t)stream);
+}
+
+int pnr_marching_cubes_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz, int64_t sx, int64_t sy,
+                            int64_t sz, double level, const double* origin, const double* spacing, const void* ws,
+                            size_t ws_bytes, double* vertices, int32_t* faces, void* stream) {
+  if (!mc_dims_ok(nx, ny, nz) || !vol || !ws || !origin || !spacing || !vertices || !faces) return PNR_E_ARG;
+  if (ws_bytes < pnr_marching_cubes_workspace_bytes(nx, ny, nz)) return PNR_E_WORKSPACE;
+  return launch_mc_emit(vol, nx, ny, nz, sx, sy, sz, level, origin, spacing, ws, vertices, faces,
+                        (hipStream_t)stream);
 }
 
 }  // extern "C"

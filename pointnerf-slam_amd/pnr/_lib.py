@@ -20,6 +20,7 @@ N_FC_PARAMS = 8
 C_DIM = 32
 MAX_K = 8
 GATHER_IDW, GATHER_TRILINEAR = 0, 1
+MASK_POSES, MASK_MAX_DEPTH, MASK_DEPTH_TEST = 0, 1, 2  # include/pnr.h PNR_MASK_*
 # decoder matmul arithmetic (include/pnr.h PNR_PREC_*)
 PRECISIONS = {'fp32': 0, 'bf16x3': 1, 'bf16': 2, 'f16x3': 3}
 # f16x3: fp32-class forward AND backward (every GEMM on 22-bit split operands with fp32
@@ -150,6 +151,17 @@ _SIGS = {
     'pnr_mlp_bwd_workspace_bytes_c': (c_size_t, [c_int64]),
     'pnr_mlp_bwd_c': (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, PtrArray, FcPtrArray,
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int32, c_void_p]),
+    'pnr_point_masks_workspace_bytes': (c_size_t, [c_int64, c_int32, c_int32]),
+    'pnr_point_masks': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_float, c_float,
+                                       c_float, c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p]),
+    'pnr_marching_cubes_workspace_bytes': (c_size_t, [c_int64, c_int64, c_int64]),
+    'pnr_marching_cubes_max_points': (c_int64, []),
+    'pnr_marching_cubes_count': (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                                ctypes.c_double, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    'pnr_marching_cubes_emit': (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                               ctypes.c_double, ctypes.c_double * 3, ctypes.c_double * 3, c_void_p,
+                                               c_size_t, c_void_p, c_void_p, c_void_p]),
     'pnr_timing_enable': (ctypes.c_int, [ctypes.c_int]),
     'pnr_timing_read': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_int64), ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(c_int64)]),

@@ -9,15 +9,29 @@ Under configs/pointNeRF_slam.yaml (`meshing.color_mesh_extraction_method: render
     Renderer.render_batch_ray with gt_depth = 0.1 in ray_batch_size chunks; the colour is clipped
     to [0,1] and stored as uint8 (:555-556).  `direct_point_query` (:513-524, the nice-slam
     setting) is eval_points(vertices)[..., :3].
-Marching cubes (skimage), mesh cleaning / culling (trimesh) and the forecast masks stay with the
-caller: they are host-side geometry, not this path.  The vertex normals the reference takes from
-open3d (`compute_vertex_normals`, open3d is not in this image) are restated by `vertex_normals` on
-the device: area-weighted sums of the unnormalised triangle normals, normalised, with (0,0,1) for a
+The geometry between the two also runs on the device (csrc/mesh.hip), because the reference's
+host libraries for it (skimage, trimesh, open3d) are not importable on this stack:
+  * `point_masks`: the seen / forecast / unseen split of Mesher.point_masks (:53-212), one kernel
+    call per points_batch_size chunk (the depth-test mode's max_depth is a per-chunk maximum);
+  * `marching_cubes`: an indexed float64 / int32 mesh with shared vertices in a deterministic order,
+    skimage's default winding, a generated crack-free case table (tools/gen_mc_table.py);
+  * `clean_mesh`: the all-unseen face cull, connected components, the small-component filter or
+    the largest component, and the compaction (:469-510), in torch ops on the device;
+  * `write_ply`, and `Mesher.get_mesh` that strings everything together.
+Two stated deviations.  Components are taken over shared VERTICES, trimesh.split takes them over
+shared edges: the two differ only where components touch at a single vertex.  And
+`get_bound_from_frames` (:214-279: open3d's TSDF volume plus a convex hull) is out of scope: get_mesh
+takes an optional `mesh_bound_mask` instead, and without it applies no hull mask (eval_points already
+returns 100 outside the scene bound).
+The vertex normals the reference takes from open3d (`compute_vertex_normals`, open3d is not in
+this image) are restated by `vertex_normals` on the device: area-weighted sums of the unnormalised triangle normals, normalised, with (0,0,1) for a
 vertex whose sum vanishes (open3d TriangleMesh::ComputeVertexNormals + MeshBase::NormalizeNormals).
 That restatement is "parity unpinned" (no open3d output is available to pin it); the colouring
 itself is pinned through render_batch_ray against the oracle (tests/test_gpu_parity.py).
 """
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 import torch
@@ -102,3 +116,304 @@ def mesh_colors(renderer, decoders, c, vertices, faces, device, method='render_r
     else:
         raise ValueError(f'pnr.mesher: unknown color_mesh_extraction_method {method!r}')
     return vertex_colors_u8(col)
+
+
+# ---- the geometry between the grid query and the colouring (csrc/mesh.hip) ------------------------
+
+# configs/pointNeRF_slam.yaml:29-38, used for the cfg['meshing'] keys a config leaves out
+MESHING_DEFAULTS = {
+    'level_set': 10, 'resolution': 256, 'eval_rec': False, 'clean_mesh': True, 'depth_test': False,
+    'mesh_coarse_level': False, 'clean_mesh_bound_scale': 1.02, 'get_largest_components': False,
+    'color_mesh_extraction_method': 'render_ray_along_normal', 'remove_small_geometry_threshold': 0.2,
+}
+
+
+def _w2c(c2w_list, device):
+    """(K,4,4) float32 on the device: np.linalg.inv of each float32 c2w on the host, as
+    src/utils/Mesher.py:90-92 / :128-130 compute it."""
+    mats = [np.linalg.inv(c2w.detach().cpu().numpy() if isinstance(c2w, torch.Tensor) else np.asarray(c2w))
+            for c2w in c2w_list]
+    if not mats:
+        return torch.empty((0, 4, 4), dtype=torch.float32, device=device)
+    return torch.from_numpy(np.stack(mats)).to(device).float().contiguous()
+
+
+def point_masks(points, keyframe_dict, estimate_c2w_list, idx, H, W, fx, fy, cx, cy, device, depth_test=False,
+                get_mask_use_all_frames=False, points_batch_size=500000):
+    """src/utils/Mesher.py:53-212 on the device: (seen, forecast, unseen) bool tensors over `points`
+    (N,3).  get_mask_use_all_frames uses the poses estimate_c2w_list[0..idx] and no depth; otherwise
+    the keyframes' 'est_c2w' and 'depth', with max_depth = 1.1 max(depth_k) (depth_test=False) or the
+    bilinear depth sample and its maximum over the points of each points_batch_size chunk
+    (depth_test=True).  One kernel call per chunk, as the reference loops."""
+    lib = _lib.load()
+    device = torch.device(device)
+    if not isinstance(points, torch.Tensor):
+        points = torch.from_numpy(np.asarray(points))
+    pts = points.detach().to(device).float().contiguous()
+    _lib.require_cuda(pts)
+    depth = max_depth = None
+    if get_mask_use_all_frames:
+        mode = _lib.MASK_POSES
+        w2c = _w2c([estimate_c2w_list[i] for i in range(0, idx + 1)], device)
+    else:
+        w2c = _w2c([kf['est_c2w'] for kf in keyframe_dict], device)
+        if depth_test:
+            mode = _lib.MASK_DEPTH_TEST
+            if len(keyframe_dict):
+                depth = torch.stack([kf['depth'].to(device).reshape(H, W) for kf in keyframe_dict]).float().contiguous()
+        else:
+            mode = _lib.MASK_MAX_DEPTH
+            if len(keyframe_dict):
+                max_depth = torch.stack([(torch.max(kf['depth']) * 1.1).to(device) for kf in keyframe_dict])
+                max_depth = max_depth.float().contiguous()
+    K, N = w2c.shape[0], pts.shape[0]
+    seen = torch.zeros(N, dtype=torch.uint8, device=device)
+    fore = torch.zeros(N, dtype=torch.uint8, device=device)
+    if K > 0:
+        for s in range(0, N, points_batch_size):
+            n = min(points_batch_size, N - s)
+            nbytes = lib.pnr_point_masks_workspace_bytes(n, K, mode)
+            ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=device)
+            _lib.check(lib.pnr_point_masks(_lib.ptr(pts[s:s + n]), n, _lib.ptr(w2c), K, H, W, fx, fy, cx, cy, mode,
+                                           _lib.ptr(depth), _lib.ptr(max_depth), _lib.ptr(seen[s:s + n]),
+                                           _lib.ptr(fore[s:s + n]), _lib.ptr(ws), nbytes, _lib.stream_of(device)),
+                       'point_masks')
+    seen, fore = seen.bool(), fore.bool()
+    return seen, fore, ~(seen | fore)
+
+
+def marching_cubes_volume(vol, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+    """Marching cubes over a float32 device tensor vol[ix, iy, iz] of any strides (no copy is made):
+    vertices (V,3) float64 = origin + (i + t) spacing with t = (level - a) / (b - a) in float64, faces
+    (F,3) int32, vertices shared, skimage's default winding, a fixed order (two runs are bitwise equal).
+    A volume without a crossing gives an empty mesh."""
+    lib = _lib.load()
+    _lib.require_cuda(vol)
+    if vol.dim() != 3 or vol.dtype != torch.float32:
+        raise ValueError('pnr.mesher: marching cubes takes a 3-d float32 volume')
+    nx, ny, nz = vol.shape
+    sx, sy, sz = vol.stride()
+    nbytes = lib.pnr_marching_cubes_workspace_bytes(nx, ny, nz)
+    if nbytes == 0:
+        raise ValueError(f'pnr.mesher: unsupported marching-cubes volume {tuple(vol.shape)} '
+                         f'(1 <= samples <= {lib.pnr_marching_cubes_max_points()})')
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=vol.device)
+    counts = torch.zeros(2, dtype=torch.int64, device=vol.device)
+    st = _lib.stream_of(vol.device)
+    _lib.check(lib.pnr_marching_cubes_count(_lib.ptr(vol), nx, ny, nz, sx, sy, sz, float(level), _lib.ptr(ws), nbytes,
+                                            counts.data_ptr(), counts.data_ptr() + 8, st), 'marching_cubes_count')
+    n_v, n_f = (int(x) for x in counts.tolist())
+    vertices = torch.empty((n_v, 3), dtype=torch.float64, device=vol.device)
+    # (a volume one sample thick has crossings but no cell: the C call still wants a faces pointer)
+    fbuf = torch.empty((max(n_f, 1), 3), dtype=torch.int32, device=vol.device)
+    faces = fbuf[:n_f]
+    if n_v > 0:
+        o = (ctypes.c_double * 3)(*[float(x) for x in origin])
+        sp = (ctypes.c_double * 3)(*[float(x) for x in spacing])
+        _lib.check(lib.pnr_marching_cubes_emit(_lib.ptr(vol), nx, ny, nz, sx, sy, sz, float(level), o, sp, _lib.ptr(ws),
+                                               nbytes, _lib.ptr(vertices), _lib.ptr(fbuf), st), 'marching_cubes_emit')
+    return vertices, faces
+
+
+def marching_cubes(z, grid_xyz, level):
+    """The marching-cubes step of Mesher.get_mesh (:437-467): `z` is the flat float32 occupancy of
+    get_grid_uniform's points, index (iy nx + ix) nz + iz, read through strides (the reference's
+    reshape + transpose copy is not made); spacing = xyz[a][2] - xyz[a][1] and origin = xyz[a][0] as
+    the reference takes them.  Returns (vertices float64 world coordinates, faces int32)."""
+    x, y, zz = (np.asarray(a, dtype=np.float64) for a in grid_xyz)
+    nx, ny, nz = len(x), len(y), len(zz)
+    if z.numel() != nx * ny * nz:
+        raise ValueError('pnr.mesher: the occupancy does not match the grid')
+    vol = z.reshape(ny, nx, nz).permute(1, 0, 2)
+    spacing = [(a[2] - a[1]) if len(a) > 2 else ((a[1] - a[0]) if len(a) > 1 else 1.0) for a in (x, y, zz)]
+    return marching_cubes_volume(vol, level, spacing, (x[0], y[0], zz[0]))
+
+
+def face_areas(vertices, faces):
+    """Triangle areas (F,) float64."""
+    f = faces.long()
+    v = vertices.double()
+    return 0.5 * torch.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]], dim=1).norm(dim=1)
+
+
+def vertex_components(n_vertices, faces):
+    """Connected-component label (the smallest vertex index of the component) of every vertex, over
+    shared vertices: min-label propagation across the faces with pointer jumping, on the device."""
+    f = faces.long()
+    label = torch.arange(n_vertices, device=faces.device)
+    if f.shape[0] == 0:
+        return label
+    flat = f.reshape(-1)
+    while True:
+        fmin = label[f].min(dim=1).values
+        new = label.scatter_reduce(0, flat, fmin.repeat_interleave(3), 'amin')
+        new = new[new]
+        if torch.equal(new, label):
+            return label
+        label = new
+
+
+def compact_mesh(vertices, faces):
+    """Drops the vertices no face names, keeping the order of both."""
+    used = torch.zeros(vertices.shape[0], dtype=torch.bool, device=vertices.device)
+    used[faces.long().reshape(-1)] = True
+    new_index = torch.cumsum(used, 0) - 1
+    return vertices[used], new_index[faces.long()].to(torch.int32)
+
+
+def clean_mesh(vertices, faces, seen_mask=None, threshold=None, largest=False):
+    """src/utils/Mesher.py:469-510 on the device: drop the faces whose three vertices are all unseen
+    (`seen_mask` (V,) bool; None = keep all), split into connected components, keep the component of
+    the largest area (`largest`) or those whose area exceeds `threshold` (already multiplied by
+    scale^2; None = keep all), and compact.  Components are taken over shared vertices (trimesh.split:
+    shared edges; the two differ only where components touch at a single vertex).  The order of the
+    kept vertices and faces is preserved; the per-component areas are summed in a fixed order."""
+    f = faces
+    if seen_mask is not None:
+        unseen = ~seen_mask.to(vertices.device).bool()
+        f = f[~unseen[f.long()].all(dim=1)]
+    if f.shape[0] > 0 and (largest or threshold is not None):
+        label = vertex_components(vertices.shape[0], f)
+        _, comp, counts = torch.unique(label[f[:, 0].long()], return_inverse=True, return_counts=True)
+        order = torch.argsort(comp, stable=True)
+        run = torch.cumsum(face_areas(vertices, f)[order], 0)
+        ends = torch.cumsum(counts, 0) - 1
+        area = run[ends]
+        area = area - torch.cat([area.new_zeros(1), area[:-1]])
+        keep = (comp == torch.argmax(area)) if largest else (area > threshold)[comp]
+        f = f[keep]
+    return compact_mesh(vertices, f)
+
+
+_clean_mesh = clean_mesh   # Mesher.get_mesh has the reference's `clean_mesh` flag of the same name
+
+
+def write_ply(path, vertices, faces, vertex_colors=None):
+    """Binary little-endian PLY: float x y z (+ uchar red green blue), faces as
+    `list uchar int vertex_indices`."""
+    v = (vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else np.asarray(vertices))
+    f = (faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces))
+    v = v.reshape(-1, 3).astype('<f4')
+    f = f.reshape(-1, 3).astype('<i4')
+    fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
+    header = ['ply', 'format binary_little_endian 1.0', f'element vertex {v.shape[0]}',
+              'property float x', 'property float y', 'property float z']
+    if vertex_colors is not None:
+        col = vertex_colors.detach().cpu().numpy() if isinstance(vertex_colors, torch.Tensor) else np.asarray(vertex_colors)
+        col = col.reshape(-1, 3).astype(np.uint8)
+        if col.shape[0] != v.shape[0]:
+            raise ValueError('pnr.mesher: one colour per vertex')
+        fields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
+        header += ['property uchar red', 'property uchar green', 'property uchar blue']
+    header += [f'element face {f.shape[0]}', 'property list uchar int vertex_indices', 'end_header']
+    vert = np.empty(v.shape[0], dtype=fields)
+    vert['x'], vert['y'], vert['z'] = v[:, 0], v[:, 1], v[:, 2]
+    if vertex_colors is not None:
+        vert['red'], vert['green'], vert['blue'] = col[:, 0], col[:, 1], col[:, 2]
+    face = np.empty(f.shape[0], dtype=[('n', 'u1'), ('idx', '<i4', (3,))])
+    face['n'] = 3
+    face['idx'] = f
+    with open(path, 'wb') as out:
+        out.write(('\n'.join(header) + '\n').encode('ascii'))
+        out.write(vert.tobytes())
+        out.write(face.tobytes())
+
+
+class Mesher(object):
+    """src/utils/Mesher.py on the HIP path: the reference's constructor arguments and get_mesh.
+
+    cfg['meshing'] keys that are absent take the values of configs/pointNeRF_slam.yaml:29-38
+    (MESHING_DEFAULTS); cfg['mapping']['marching_cubes_bound'] falls back to cfg['mapping']['bound'].
+    No dataset reader is built.  Out of scope: get_bound_from_frames (open3d's TSDF volume plus a
+    convex hull) -- see get_mesh's `mesh_bound_mask`."""
+
+    def __init__(self, cfg, args, slam, points_batch_size=500000, ray_batch_size=100000):
+        self.points_batch_size = points_batch_size
+        self.ray_batch_size = ray_batch_size
+        self.renderer = slam.renderer
+        self.coarse = cfg.get('coarse', False)
+        self.scale = cfg['scale']
+        self.occupancy = cfg.get('occupancy', False)
+        m = {**MESHING_DEFAULTS, **cfg.get('meshing', {})}
+        self.resolution = m['resolution']
+        self.level_set = m['level_set']
+        self.clean_mesh_bound_scale = m['clean_mesh_bound_scale']
+        self.remove_small_geometry_threshold = m['remove_small_geometry_threshold']
+        self.color_mesh_extraction_method = m['color_mesh_extraction_method']
+        self.get_largest_components = m['get_largest_components']
+        self.depth_test = m['depth_test']
+        self.bound = slam.bound
+        self.nice = False
+        self.verbose = getattr(slam, 'verbose', False)
+        mapping = cfg['mapping']
+        self.marching_cubes_bound = torch.from_numpy(
+            np.array(mapping.get('marching_cubes_bound', mapping['bound'])) * self.scale)
+        self.H, self.W, self.fx, self.fy, self.cx, self.cy = slam.H, slam.W, slam.fx, slam.fy, slam.cx, slam.cy
+
+    def point_masks(self, input_points, keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames=False):
+        """Mesher.point_masks (:53-212); bool tensors on the device."""
+        return point_masks(input_points, keyframe_dict, estimate_c2w_list, idx, self.H, self.W, self.fx, self.fy,
+                           self.cx, self.cy, device, depth_test=self.depth_test,
+                           get_mask_use_all_frames=get_mask_use_all_frames, points_batch_size=self.points_batch_size)
+
+    def eval_points(self, p, decoders, c=None, stage='color', device='cuda:0'):
+        """Mesher.eval_points (:281-319): raw (P,4) in points_batch_size chunks."""
+        out = [self.renderer.eval_points(pi, decoders, c, stage, device) for pi in torch.split(p, self.points_batch_size)]
+        return torch.cat(out, 0) if out else torch.empty((0, 4), device=p.device)
+
+    def get_grid_uniform(self, resolution):
+        return get_grid_uniform(self.marching_cubes_bound, resolution)
+
+    def get_mesh(self, mesh_out_file, c, decoders, keyframe_dict, estimate_c2w_list, idx, device='cuda:0',
+                 show_forecast=False, color=True, clean_mesh=True, get_mask_use_all_frames=False,
+                 mesh_bound_mask=None):
+        """Mesher.get_mesh (:349-574): extracts the mesh, writes it to `mesh_out_file` (binary PLY) and
+        returns (vertices (V,3) float64 divided by scale, faces (F,3) int32, colors (V,3) uint8 or None)
+        on the device; None when the level set has no surface (the reference's except branch).
+
+        `mesh_bound_mask` stands in for the reference's convex hull (get_bound_from_frames, out of
+        scope): a bool tensor over the grid points, or a callable points (N,3) -> bool (N,).  With
+        show_forecast=False it sets the occupancy outside it to 100 (:433); with show_forecast=True
+        a callable also culls the faces whose vertices all lie outside it (:475-485).  Without it no
+        hull mask is applied."""
+        with torch.no_grad():
+            device = torch.device(device)
+            grid = self.get_grid_uniform(self.resolution)
+            points = grid['grid_points'].to(device)
+            masks = dict(keyframe_dict=keyframe_dict, estimate_c2w_list=estimate_c2w_list, idx=idx, device=device,
+                         get_mask_use_all_frames=get_mask_use_all_frames)
+            if show_forecast:
+                seen, forecast, unseen = self.point_masks(points, **masks)
+                z = torch.zeros(points.shape[0], dtype=torch.float32, device=device)
+                z[forecast] = self.eval_points(points[forecast], decoders, c, 'coarse', device)[:, -1] + 0.2
+                z[seen] = self.eval_points(points[seen], decoders, c, 'fine', device)[:, -1]
+                z[unseen] = -100
+            else:
+                z = self.eval_points(points, decoders, c, 'fine', device)[:, -1].contiguous()
+                if mesh_bound_mask is not None:
+                    inside = mesh_bound_mask(points) if callable(mesh_bound_mask) else mesh_bound_mask
+                    z[~inside.to(device).bool()] = 100
+            vertices, faces = marching_cubes(z, grid['xyz'], self.level_set)
+            if vertices.shape[0] == 0:
+                print('marching_cubes error. Possibly no surface extracted from the level set.')
+                return None
+            if clean_mesh:
+                if show_forecast:
+                    keep = mesh_bound_mask(vertices).to(device).bool() if callable(mesh_bound_mask) else None
+                else:
+                    keep = self.point_masks(vertices, **masks)[0]
+                vertices, faces = _clean_mesh(
+                    vertices, faces, keep, largest=self.get_largest_components,
+                    threshold=self.remove_small_geometry_threshold * self.scale * self.scale)
+            colors = None
+            if color:
+                colors = torch.from_numpy(mesh_colors(self.renderer, decoders, c, vertices, faces, device,
+                                                      self.color_mesh_extraction_method)).to(device)
+                if show_forecast:   # cyan for the forecast region
+                    forecast = self.point_masks(vertices, **masks)[1]
+                    colors[forecast] = torch.tensor([0, 255, 255], dtype=torch.uint8, device=device)
+            vertices = vertices / self.scale
+            write_ply(mesh_out_file, vertices, faces, colors)
+            if self.verbose:
+                print('Saved mesh at', mesh_out_file)
+            return vertices, faces, colors

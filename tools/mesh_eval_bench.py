@@ -7,10 +7,20 @@ Grid: R^3 float32 points over the room0 bound padded by 0.05 (np.linspace per ax
 ravel, as get_grid_uniform), queried through pnr.Renderer.eval_points in 500,000-point chunks
 (points_batch_size), as the Mesher does.  Parity: 4,096 random grid points against the oracle's
 eval_points (CPU).  Prints one JSON line with the decoder FLOP rate (443,438 FLOP per point).
+
+--extract adds the device geometry between the query and the colouring (pnr.mesher: point masks,
+marching cubes, cleaning) at the same resolution, with synthetic keyframes (--keyframes poses yawed
+about the scene pose, 680x1200 depth images in 0.3-0.6 scene units) under an 'extract' key.  Each
+step is a child process of its own under `timeout` (--step-timeout seconds); after a child that
+fails or runs out of time no further child is started and the tool exits non-zero.  The
+marching-cubes bytes are the traffic the algorithm needs: the volume read once (4 B/sample), the
+per-sample word written and read once (4 + 4 B), 24 B per vertex and 12 B per face written; the rate
+is those bytes over the time of the whole call (three launches and the host read of the counts).
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 import types
@@ -25,12 +35,104 @@ sys.path.insert(0, REPO)
 from bench import load_scene, FLOP_PER_POINT_FWD  # noqa: E402
 
 
+EXTRACT_STEPS = ('masks', 'mc', 'clean')
+HBM_BYTES_PER_S = 8e12
+
+
+def timed(fn, iters):
+    """Mean seconds of fn() over `iters` calls after one warm-up call; every call ends in a device
+    synchronise."""
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        out = fn()
+        torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters, out
+
+
+def extract_step(step, args):
+    """One --extract step in this process: prints its JSON line."""
+    import pnr
+    dev = torch.device('cuda:0')
+    bound, pose, params = load_scene()
+    slam = types.SimpleNamespace(bound=bound, H=680, W=1200, fx=600., fy=600., cx=599.5, cy=339.5)
+    r = pnr.Renderer(dict(pnr.ROOM0_CFG), None, slam)
+    dec = pnr.get_model(pnr.ROOM0_CFG, nice=False)
+    dec.load_state_dict(params)
+    dec = dec.to(dev)
+    slam.renderer = r
+    cfg = dict(pnr.ROOM0_CFG, meshing={'resolution': args.resolution})
+    cfg['mapping'] = dict(cfg['mapping'], marching_cubes_bound=(bound.numpy() / cfg['scale']).tolist())
+    m = pnr.Mesher(cfg, None, slam)
+    g = torch.Generator().manual_seed(0)
+    c2w0 = torch.as_tensor(pose, dtype=torch.float32).reshape(4, 4)
+    keyframes = []
+    for k in range(args.keyframes):
+        a = 2 * np.pi * k / args.keyframes
+        rot = torch.eye(4)
+        rot[0, 0], rot[0, 2], rot[2, 0], rot[2, 2] = np.cos(a), np.sin(a), -np.sin(a), np.cos(a)
+        c2w = c2w0.clone()
+        c2w[:3, :3] = rot[:3, :3] @ c2w0[:3, :3]
+        keyframes.append({'est_c2w': c2w, 'depth': (0.3 + 0.3 * torch.rand((680, 1200), generator=g)).to(dev)})
+    est = torch.stack([kf['est_c2w'] for kf in keyframes])
+    grid = m.get_grid_uniform(m.resolution)
+    points = grid['grid_points'].to(dev)
+    n = points.shape[0]
+    out = {'points': n, 'keyframes': args.keyframes}
+    if step == 'masks':
+        for name, kw in (('poses', dict(get_mask_use_all_frames=True)), ('maxdepth', {}), ('depthtest', {})):
+            m.depth_test = name == 'depthtest'
+            t, (seen, fore, unseen) = timed(lambda: m.point_masks(points, keyframes, est, len(keyframes) - 1, dev, **kw),
+                                            args.iters)
+            out[name] = {'ms': round(t * 1e3, 3), 'seen': int(seen.sum()), 'forecast': int(fore.sum()),
+                         'unseen': int(unseen.sum())}
+    else:
+        z = m.eval_points(points, dec, None, 'fine', dev)[:, -1].contiguous()
+        t, (v, f) = timed(lambda: pnr.mesher.marching_cubes(z, grid['xyz'], m.level_set), args.iters)
+        out.update({'vertices': v.shape[0], 'faces': f.shape[0]})
+        if step == 'mc':
+            nbytes = 12 * n + 24 * v.shape[0] + 12 * f.shape[0]
+            out.update({'ms': round(t * 1e3, 3), 'bytes': nbytes, 'gbytes_per_s': round(nbytes / t / 1e9, 1),
+                        'share_of_8TBps': float(f'{nbytes / t / HBM_BYTES_PER_S:.3g}')})
+        else:
+            seen = m.point_masks(v, keyframes, est, len(keyframes) - 1, dev)[0]
+            thr = m.remove_small_geometry_threshold * m.scale * m.scale
+            t, (cv, cf) = timed(lambda: pnr.mesher.clean_mesh(v, f, seen, threshold=thr), args.iters)
+            out.update({'ms': round(t * 1e3, 3), 'seen_vertices': int(seen.sum()), 'kept_vertices': cv.shape[0],
+                        'kept_faces': cf.shape[0]})
+    print(json.dumps({'extract_step': step, **out}))
+
+
+def run_extract(args):
+    """Each step in a child process under its own `timeout`; stops at the first failure."""
+    res = {}
+    for step in EXTRACT_STEPS:
+        cmd = ['timeout', '-k', '10', str(args.step_timeout), sys.executable, os.path.abspath(__file__),
+               '--extract-step', step, '--resolution', str(args.resolution), '--iters', str(args.iters),
+               '--keyframes', str(args.keyframes)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+        if p.returncode != 0:
+            sys.stdout.write(p.stdout)
+            raise SystemExit(f'mesh_eval_bench: extract step {step!r} ended with status {p.returncode}; '
+                             'no further step started')
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith('{"extract_step"')][-1]
+        res[step] = {k: v for k, v in json.loads(line).items() if k != 'extract_step'}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--resolution', type=int, default=256)
     ap.add_argument('--precision', default=None)
     ap.add_argument('--iters', type=int, default=3)
+    ap.add_argument('--extract', action='store_true', help='also time the masks, marching cubes and cleaning')
+    ap.add_argument('--extract-step', choices=EXTRACT_STEPS, help='(child of --extract) run one step here')
+    ap.add_argument('--keyframes', type=int, default=8)
+    ap.add_argument('--step-timeout', type=int, default=180)
     args = ap.parse_args()
+    if args.extract_step:
+        return extract_step(args.extract_step, args)
     import pnr
     from oracle import ref_render as ref
     dev = torch.device('cuda:0')
@@ -66,10 +168,15 @@ def main():
     rr = ref.eval_points(params, grid[sel], bound)
     og = out[sel.to(dev)].cpu()
     err = float((og - rr).abs().max() / rr.abs().max())
-    print(json.dumps({'metric': 'Mesher dense-grid decoder query points/sec', 'value': round(n / t, 1),
-                      'unit': 'points/s', 'ms': round(t * 1e3, 3), 'points': n, 'resolution': R,
-                      'tflops': round(n * FLOP_PER_POINT_FWD / t / 1e12, 1), 'precision': r.precision,
-                      'parity': {'points': 4096, 'max_abs_err_over_max': float(f'{err:.3g}')}}))
+    res = {'metric': 'Mesher dense-grid decoder query points/sec', 'value': round(n / t, 1),
+           'unit': 'points/s', 'ms': round(t * 1e3, 3), 'points': n, 'resolution': R,
+           'tflops': round(n * FLOP_PER_POINT_FWD / t / 1e12, 1), 'precision': r.precision,
+           'parity': {'points': 4096, 'max_abs_err_over_max': float(f'{err:.3g}')}}
+    if args.extract:
+        del out, gd
+        torch.cuda.empty_cache()
+        res['extract'] = run_extract(args)
+    print(json.dumps(res))
 
 
 if __name__ == '__main__':
