@@ -383,6 +383,47 @@ int pnr_map_step(const pnr_render_params* prm, const float* packed, const float*
                  float w_reg, double* loss, float* const* grads, void* workspace, size_t ws_bytes, void* bwd_ws,
                  size_t bwd_bytes, void* loss_ws, void* stream);
 
+/* The step with its optimiser (additions to ABI 14): pnr_map_step whose weight-gradient reduction also
+ * takes the Adam step of pnr_adam_multi_dev (one segment) on every element it has just summed, and
+ * leaves the weight scales of the next PNR_PACK_F16X3_ONLY pack -- ONE launch (k_reduce_adam_multi)
+ * where the reduction, the Adam kernel and the pack's scale stage were three.  Bit for bit what
+ * pnr_map_step + pnr_adam_multi_dev + pnr_mlp_pack2's scales give.
+ *   p, g: the flat parameter / gradient buffers (n floats; the eleven grads[i] must tile [g, g + n)
+ *   exactly -- only the elements the reduction owns are stepped -- else PNR_E_ARG); m, v: the moments
+ *   of [0, n); step2 as pnr_adam_multi_dev;
+ *   scales: pnr_step_tail_floats() floats, ZERO-FILLED before the first use and owned by this step
+ *   (not shared by concurrent calls): floats [0, 5) receive the scales of W0..W3, Wo and [5, 10)
+ *   their inverses (the rest is the kernel's hand-off scratch), for pnr_mlp_pack_scaled.
+ * The fused tail runs, and *fused = 1, only when the precision is a split one, grads is given, there
+ * are no neural points, n > 0, n_rays > 0, the backward is a single chunk and prm->grads_overwrite
+ * is set; otherwise the call is pnr_map_step unchanged, *fused = 0, and the caller runs Adam. */
+typedef struct pnr_adam_tail {
+  float* p;
+  float* g;
+  float* m;
+  float* v;
+  int64_t n;
+  float lr, beta1, beta2, eps;
+  int32_t* step2;
+  float* scales;
+} pnr_adam_tail;
+size_t pnr_step_tail_floats(void);
+int pnr_map_step_adam(const pnr_render_params* prm, const float* packed, const float* rays_o, const float* rays_d,
+                      const float* gt_depth, const float* gt_color, const float* t_rand, int64_t n, float w_color,
+                      float w_reg, double* loss, float* const* grads, void* workspace, size_t ws_bytes, void* bwd_ws,
+                      size_t bwd_bytes, void* loss_ws, const pnr_adam_tail* tail, int32_t* fused, void* stream);
+/* pnr_mlp_pack2(PNR_PACK_F16X3_ONLY) with the scales given (scales[0..5) and their inverses
+ * [5..10), device floats, e.g. pnr_map_step_adam's): the images' launch alone, which also copies the
+ * ten floats into the image's raw table.  Bit for bit the full pack when the scales are the tensors'. */
+int pnr_mlp_pack_scaled(const float* const* params, float* packed, const float* scales, void* stream);
+/* pnr_window_sample and pnr_mlp_pack_scaled as ONE launch (blocks of either kind: the two do not depend
+ * on each other, and each sat at the launch-latency floor).  Same outputs as the two calls. */
+int pnr_window_sample_pack(uint64_t seed, void* state, int64_t n, int64_t n_per_frame, int32_t H, int32_t W, float fx,
+                           float fy, float cx, float cy, const float* c2w, const float* depth, const float* color,
+                           int32_t n_samples, float* rays_o, float* rays_d, float* gt_depth, float* gt_color,
+                           float* t_rand, int64_t* idx, float* far_clamp, const float* const* params, float* packed,
+                           const float* scales, void* stream);
+
 /* ---- mesh extraction (src/utils/Mesher.py:349-574; additions to ABI 14) -------------------------
  * Mesher.point_masks (:53-212) for one chunk of P float32 points (the caller splits by
  * points_batch_size as the reference does: PNR_MASK_DEPTH_TEST's max_depth is a maximum over the

@@ -18,7 +18,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "pnr_internal.h"
@@ -304,8 +306,11 @@ int zero_weight_grads(float* const* grads, float* const* g_fc, hipStream_t st) {
 
 // Shared backward core over P points with saved activations `sv` and dL/draw in b.g_out.
 int mlp_backward_core(int prec, const float* packed, const SaveArgs& sv, int64_t P, BwdWS& b, float* const* grads,
-                      bool want_gx, hipStream_t st, const FeatBwd* fb = nullptr, bool overwrite = false) {
+                      bool want_gx, hipStream_t st, const FeatBwd* fb = nullptr, bool overwrite = false,
+                      const AdamTail* tail = nullptr) {
   const bool split = prec != PNR_PREC_FP32;  // f16x3 delta chain + f16x3 weight-gradient GEMMs
+  // the fused reduce + Adam tail: the caller has checked a split precision, stored gradients, one chunk
+  if (tail && (!split || !grads || !overwrite || fb || P <= 0 || P > b.C)) return PNR_E_ARG;
   if (overwrite && (!split || P == 0)) {  // the fp32 GEMMs add into C: store = add into zeroed gradients
     if (int rc = zero_weight_grads(grads, fb ? fb->g_fc : nullptr, st)) return rc;
     overwrite = false;
@@ -462,7 +467,7 @@ int mlp_backward_core(int prec, const float* packed, const SaveArgs& sv, int64_t
     }
     if (overwrite && p0 == 0)  // the first chunk stores its sums; the later chunks add to them
       for (int i = 0; i < nj; ++i) jobs[i].overwrite = 1;
-    if (rc == 0) rc = launch_part_reduce_multi(jobs, nj, st);
+    if (rc == 0) rc = launch_part_reduce_multi(jobs, nj, st, tail);
     if (rc) return rc;
   }
   return hip_status(hipGetLastError());
@@ -983,7 +988,7 @@ int map_fwd_core(const pnr_render_params* prm, const float* packed, const float*
 // fused tail already wrote it: `fine_done`), the delta chain / weight gradients and the gather backward
 int map_bwd_core(const pnr_render_params* prm, const float* packed, const float* rays_d, int64_t n, const MapWS& w,
                  BwdWS& b, const double* g_depth, const float* g_rgb, const float* g_sigma, float* const* grads,
-                 bool fine_done, hipStream_t st) {
+                 bool fine_done, hipStream_t st, const AdamTail* tail = nullptr) {
   const int S = prm->n_samples, I = prm->n_importance;
   const double* zi = w.z + n * S;
   const float4* x4 = w.save.xP;
@@ -1001,7 +1006,7 @@ int map_bwd_core(const pnr_render_params* prm, const float* packed, const float*
   }
   FeatBwd fb{pts ? pts->fc_packed : nullptr, w.c, pts ? pts->g_fc : nullptr};
   rc = mlp_backward_core(prm->precision, packed, w.save, w.ld, b, grads, false, st, pts ? &fb : nullptr,
-                         prm->grads_overwrite != 0);
+                         prm->grads_overwrite != 0, tail);
   if (rc) return rc;
   if (pts)
     rc = launch_gather_bwd(*pts, nullptr, kPtsX4, x4, w.ld, w.nidx, w.nw, w.c, b.g_c, nullptr, true, b.gws, b.gws_bytes,
@@ -1083,12 +1088,16 @@ size_t pnr_map_step_workspace_bytes(const pnr_render_params* prm, int64_t n_rays
   return c.off;
 }
 
-int pnr_map_step(const pnr_render_params* prm, const float* packed, const float* rays_o, const float* rays_d,
-                 const float* gt_depth, const float* gt_color, const float* t_rand, int64_t n, float w_color,
-                 float w_reg, double* loss, float* const* grads, void* workspace, size_t ws_bytes, void* bwd_ws,
-                 size_t bwd_bytes, void* loss_ws, void* stream) {
+// pnr_map_step, and pnr_map_step_adam when `tail` is given: *fused = 1 when the weight-gradient
+// reduction took the Adam step (k_reduce_adam_multi), 0 when the call ran pnr_map_step's launches
+static int map_step_impl(const pnr_render_params* prm, const float* packed, const float* rays_o, const float* rays_d,
+                         const float* gt_depth, const float* gt_color, const float* t_rand, int64_t n, float w_color,
+                         float w_reg, double* loss, float* const* grads, void* workspace, size_t ws_bytes,
+                         void* bwd_ws, size_t bwd_bytes, void* loss_ws, const pnr_adam_tail* tail, int32_t* fused,
+                         void* stream) {
   if (!valid_map_prm(prm) || !packed || n < 0 || !loss || !loss_ws) return PNR_E_ARG;
   hipStream_t st = (hipStream_t)stream;
+  if (fused) *fused = 0;
   if (grads)
     for (int i = 0; i < PNR_N_PARAMS; ++i)
       if (!grads[i]) return PNR_E_ARG;
@@ -1107,6 +1116,13 @@ int pnr_map_step(const pnr_render_params* prm, const float* packed, const float*
   const pnr_points* pts = prm->points;
   BwdWS b = carve_bwd(w.ld, n, bwd_ws, &bneed, pts != nullptr, true, n_pts(prm));
   if (ws_bytes < c.off || bwd_bytes < bneed) return PNR_E_WORKSPACE;
+  AdamTail at{};
+  const bool tail_ok = tail && prm->precision != PNR_PREC_FP32 && grads && !pts && tail->n > 0 && w.ld <= b.C &&
+                       prm->grads_overwrite && part_reduce_vec_enabled();
+  if (tail_ok) {
+    at = AdamTail{tail->p, tail->g, tail->m, tail->v, tail->n, 0, tail->lr, tail->beta1, tail->beta2, tail->eps,
+                  tail->step2, tail->scales, {grads[1], grads[3], grads[5], grads[7], grads[9]}};
+  }
   const bool fuse = n <= fine_loss_max_rays();
   int rc = map_fwd_core(prm, packed, rays_o, rays_d, gt_depth, t_rand, n, w, sw.depth, sw.var, sw.rgb,
                         fuse ? nullptr : sw.sigma, !fuse, st);
@@ -1125,7 +1141,57 @@ int pnr_map_step(const pnr_render_params* prm, const float* packed, const float*
                          sw.g_depth, sw.g_rgb, sw.g_sigma, st);
   }
   if (rc) return rc;
-  return map_bwd_core(prm, packed, rays_d, n, w, b, sw.g_depth, sw.g_rgb, sw.g_sigma, grads, fuse, st);
+  rc = map_bwd_core(prm, packed, rays_d, n, w, b, sw.g_depth, sw.g_rgb, sw.g_sigma, grads, fuse, st,
+                    tail_ok ? &at : nullptr);
+  if (rc == 0 && tail_ok && fused) *fused = 1;
+  return rc;
+}
+
+int pnr_map_step(const pnr_render_params* prm, const float* packed, const float* rays_o, const float* rays_d,
+                 const float* gt_depth, const float* gt_color, const float* t_rand, int64_t n, float w_color,
+                 float w_reg, double* loss, float* const* grads, void* workspace, size_t ws_bytes, void* bwd_ws,
+                 size_t bwd_bytes, void* loss_ws, void* stream) {
+  return map_step_impl(prm, packed, rays_o, rays_d, gt_depth, gt_color, t_rand, n, w_color, w_reg, loss, grads,
+                       workspace, ws_bytes, bwd_ws, bwd_bytes, loss_ws, nullptr, nullptr, stream);
+}
+
+size_t pnr_step_tail_floats(void) { return (size_t)kStepTailFloats; }
+
+int pnr_map_step_adam(const pnr_render_params* prm, const float* packed, const float* rays_o, const float* rays_d,
+                      const float* gt_depth, const float* gt_color, const float* t_rand, int64_t n, float w_color,
+                      float w_reg, double* loss, float* const* grads, void* workspace, size_t ws_bytes, void* bwd_ws,
+                      size_t bwd_bytes, void* loss_ws, const pnr_adam_tail* tail, int32_t* fused, void* stream) {
+  static const int64_t dec_n[PNR_N_PARAMS] = {3 * kFourier, kHidden * kFourier, kHidden, kHidden * kHidden, kHidden,
+                                              kHidden * kHidden, kHidden, kHidden * kHidden, kHidden, 4 * kHidden, 4};
+  if (!tail || !fused || tail->n < 0 || !tail->step2 || !tail->scales ||
+      reinterpret_cast<uintptr_t>(tail->scales) % 8 != 0)
+    return PNR_E_ARG;
+  if (tail->n > 0 && (!tail->p || !tail->g || !tail->m || !tail->v)) return PNR_E_ARG;
+  if (grads) {
+    // the element index of the Adam step is the gradient's address minus g, and the reduction's owners
+    // are the only elements stepped: the eleven tensors must tile [g, g + n) exactly
+    std::pair<int64_t, int64_t> span[PNR_N_PARAMS];
+    for (int i = 0; i < PNR_N_PARAMS; ++i) {
+      if (!grads[i] || grads[i] < tail->g || grads[i] + dec_n[i] > tail->g + tail->n) return PNR_E_ARG;
+      span[i] = {grads[i] - tail->g, dec_n[i]};
+    }
+    std::sort(span, span + PNR_N_PARAMS);
+    int64_t at = 0;
+    for (int i = 0; i < PNR_N_PARAMS; ++i) {
+      if (span[i].first != at) return PNR_E_ARG;
+      at += span[i].second;
+    }
+    if (at != tail->n) return PNR_E_ARG;
+  }
+  return map_step_impl(prm, packed, rays_o, rays_d, gt_depth, gt_color, t_rand, n, w_color, w_reg, loss, grads,
+                       workspace, ws_bytes, bwd_ws, bwd_bytes, loss_ws, tail, fused, stream);
+}
+
+int pnr_mlp_pack_scaled(const float* const* params, float* packed, const float* scales, void* stream) {
+  if (!check_params(params) || !packed || !scales) return PNR_E_ARG;
+  RawParams rp;
+  for (int i = 0; i < PNR_N_PARAMS; ++i) rp.p[i] = params[i];
+  return launch_pack_scaled(rp, packed, scales, (hipStream_t)stream);
 }
 
 // ---- neural points ---------------------------------------------------------------------------
@@ -1286,6 +1352,24 @@ int pnr_window_sample(uint64_t seed, void* state, int64_t n, int64_t n_per_frame
     return PNR_E_ARG;
   return launch_window_sample(seed, state, n, n_per_frame, H, W, fx, fy, cx, cy, c2w, depth, color, n_samples, rays_o,
                               rays_d, gt_depth, gt_color, t_rand, idx, far_clamp, (hipStream_t)stream);
+}
+
+int pnr_window_sample_pack(uint64_t seed, void* state, int64_t n, int64_t n_per_frame, int32_t H, int32_t W, float fx,
+                           float fy, float cx, float cy, const float* c2w, const float* depth, const float* color,
+                           int32_t n_samples, float* rays_o, float* rays_d, float* gt_depth, float* gt_color,
+                           float* t_rand, int64_t* idx, float* far_clamp, const float* const* params, float* packed,
+                           const float* scales, void* stream) {
+  if (n < 0 || H <= 0 || W <= 0 || n_per_frame <= 0 || n_samples < 0) return PNR_E_ARG;
+  if ((int64_t)H * W >= (1LL << 32)) return PNR_E_ARG;
+  if (n > 0 && (!state || !c2w || !depth || !color || !rays_o || !rays_d || !gt_depth || !gt_color ||
+                (n_samples > 0 && !t_rand)))
+    return PNR_E_ARG;
+  if (!check_params(params) || !packed || !scales) return PNR_E_ARG;
+  RawParams rp;
+  for (int i = 0; i < PNR_N_PARAMS; ++i) rp.p[i] = params[i];
+  return launch_sample_pack(seed, state, n, n_per_frame, H, W, fx, fy, cx, cy, c2w, depth, color, n_samples, rays_o,
+                            rays_d, gt_depth, gt_color, t_rand, idx, far_clamp, rp, packed, scales,
+                            (hipStream_t)stream);
 }
 
 int pnr_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,

@@ -70,7 +70,7 @@ __device__ __forceinline__ void glds16s_x8(const char* src, uint32_t voff, uint3
       "s_mov_b32 m0, %0"
       : "=&s"(keep)
       : "v"(voff), "v"(voff2), "s"(src), "s"(src + 8192), "s"(src + 16384), "s"(src + 24576), "s"(lds_byte)
-      : "memory");
+      : "memory", "scc");  // s_add_u32 writes SCC
 }
 
 // Four LDS-DMA pieces of 1 KB per wave, 8 KB apart in the source and in LDS (one weight step of the
@@ -88,7 +88,7 @@ __device__ __forceinline__ void glds16s_x4(const char* src, uint32_t voff, uint3
       "s_mov_b32 m0, %0"
       : "=&s"(keep)
       : "v"(voff), "v"(voff2), "s"(src), "s"(src + 16384), "s"(lds_byte)
-      : "memory");
+      : "memory", "scc");  // s_add_u32 writes SCC
 }
 
 // 16-B store of a training save (activations, deltas), read back only by a later kernel.

@@ -5,9 +5,11 @@
 #include <mutex>
 #include <unordered_map>
 
+#include "adam.h"
 #include "mlp16.h"
 #include "mlp16w.h"
 #include "pack_fp32.h"
+#include "window_sample.h"
 
 namespace pnr {
 
@@ -53,15 +55,7 @@ __device__ __forceinline__ void wscale_block(const ScaleArgs& a, const int b) {
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int k = 1; k < nw; ++k) red[0] = fmaxf(red[0], red[k]);
-    int e = 20;
-    if (red[0] > 0.f) {
-      int ex;
-      frexpf(16384.f / red[0], &ex);  // 16384/max = f 2^ex, f in [0.5,1)
-      e = ex - 1;                     // 2^e <= 16384/max
-      e = e < -20 ? -20 : (e > 20 ? 20 : e);
-    }
-    a.scl[b] = ldexpf(1.f, e);
-    a.inv[b] = ldexpf(1.f, -e);
+    wscale_from_max(red[0], a.scl + b, a.inv + b);  // adam.h (shared with k_reduce_adam_multi)
   }
 }
 __global__ __launch_bounds__(1024) void k_wscale(ScaleArgs a) { wscale_block(a, blockIdx.x); }
@@ -76,7 +70,8 @@ __device__ __forceinline__ uint16_t part_bits(float x, int part) {
 // element (T, s, part, lane, j) of a weight fragment image for a layer with A[row][k]:
 // row = 32T + (lane&31), k = 32kc + perm(8s+j, lane>>5).  img 0: BF16X3, 1: BF16, 2: F16X3.
 __device__ __forceinline__ void pack16_at(const RawParams& rp, uint16_t* __restrict__ bf2, uint16_t* __restrict__ bf1,
-                                          uint16_t* __restrict__ h2, float* __restrict__ raw, const int64_t idx64) {
+                                          uint16_t* __restrict__ h2, float* __restrict__ raw, const float* __restrict__ scl,
+                                          const int64_t idx64) {
   constexpr int n2 = (int)(bf_main_bytes(2) / 2), n1 = (int)(bf_main_bytes(1) / 2);
   static_assert(2LL * n2 + n1 < (1LL << 30), "32-bit pack indices");
   if (idx64 < 2 * n2 + n1) {
@@ -118,7 +113,7 @@ __device__ __forceinline__ void pack16_at(const RawParams& rp, uint16_t* __restr
         v = row < 4 ? rp.p[9][row * kHidden + k] : 0.f;
       }
     }
-    if (img == 2) h2[e0] = part_bits<_Float16>(v * raw[kRawScl + tensor], part);
+    if (img == 2) h2[e0] = part_bits<_Float16>(v * scl[tensor], part);
     else (img == 0 ? bf2 : bf1)[e0] = part_bits<__bf16>(v, part);
     return;
   }
@@ -144,7 +139,7 @@ __device__ __forceinline__ void pack16_at(const RawParams& rp, uint16_t* __restr
 // Transposed f16x3 images of the delta chain (element e of the backward stream), each tensor
 // scaled by the forward image's power of two (raw[kRawScl + tensor], k_wscale)
 __device__ __forceinline__ void pack16_bwd_at(const RawParams& rp, uint16_t* __restrict__ out,
-                                              const float* __restrict__ raw, const int64_t e) {
+                                              const float* __restrict__ scl, const int64_t e) {
   if (e >= kBwdBytes / 2) return;
   static_assert(kBwdBytes < (1LL << 31), "32-bit pack indices");
   const int byte = 2 * (int)e;
@@ -175,7 +170,7 @@ __device__ __forceinline__ void pack16_bwd_at(const RawParams& rp, uint16_t* __r
       tensor = 0;
     }
   }
-  out[e] = part_bits<_Float16>(v * raw[kRawScl + tensor], part);
+  out[e] = part_bits<_Float16>(v * scl[tensor], part);
 }
 
 // The 16-point-wave forward image (mlp16w.h, element e of kW16Bytes / 2): 27 hidden steps of
@@ -183,7 +178,7 @@ __device__ __forceinline__ void pack16_bwd_at(const RawParams& rp, uint16_t* __r
 // Fourier layer and 32kc + w16_kmap(8(lane >> 4) + j) for the hidden ones; then Wo (rows 0..3 of 16) per
 // h4 input tile [kc 8][part 2][lane 64][j 8].  f16x3 parts under the forward image's scales.
 __device__ __forceinline__ void pack16w_at(const RawParams& rp, uint16_t* __restrict__ out,
-                                           const float* __restrict__ raw, const int e) {
+                                           const float* __restrict__ scl, const int e) {
   constexpr int hstep = (int)(kW16StepBytes / 2);
   static_assert(kW16Bytes / 2 < (1LL << 31), "32-bit pack indices");
   if (e >= (int)(kW16Bytes / 2)) return;
@@ -215,7 +210,7 @@ __device__ __forceinline__ void pack16w_at(const RawParams& rp, uint16_t* __rest
     v = row < 4 ? rp.p[9][row * kHidden + 32 * kc + w16_kmap(8 * (lane >> 4) + j)] : 0.f;
     tensor = 4;
   }
-  out[e] = part_bits<_Float16>(v * raw[kRawScl + tensor], part);
+  out[e] = part_bits<_Float16>(v * scl[tensor], part);
 }
 
 // The weight images of every precision in two launches (the Mapper repacks once per iteration, and
@@ -228,6 +223,13 @@ __device__ __forceinline__ void pack16w_at(const RawParams& rp, uint16_t* __rest
 // flags (pnr_mlp_pack2 / pnr_fc_pack2): PNR_PACK_F16X3_ONLY -- only the images the f16x3 kernels read
 // (stage 1: the scale blocks alone, no fp32 image; stage 2: no bf16 images).
 constexpr int kPack1Blocks = 248;
+struct PackStage2 {
+  RawParams rp;
+  float* packed;
+  const float* scales;
+  int nb_bwd, nb16;
+  int64_t base16;
+};
 __global__ __launch_bounds__(1024) void k_pack_stage1(ScaleArgs sa, RawParams rp, float* __restrict__ packed,
                                                       int nscale) {
   if ((int)blockIdx.x < nscale) {
@@ -238,17 +240,42 @@ __global__ __launch_bounds__(1024) void k_pack_stage1(ScaleArgs sa, RawParams rp
   for (int64_t i = (int64_t)(blockIdx.x - nscale) * 1024 + threadIdx.x; i < kPackedFloats; i += stride)
     pack_fp32_at(rp, packed, i);
 }
-__global__ __launch_bounds__(256) void k_pack_stage2(RawParams rp, float* __restrict__ packed, int nb_bwd,
-                                                     int nb16, int64_t base16) {
-  float* raw = packed + kOffRaw;
-  if ((int)blockIdx.x >= nb_bwd + nb16)  // the 16-point-wave forward image (after the raw table)
-    pack16w_at(rp, reinterpret_cast<uint16_t*>(packed + kOffW16), raw, ((int)blockIdx.x - nb_bwd - nb16) * 256 + threadIdx.x);
-  else if ((int)blockIdx.x < nb_bwd)
-    pack16_bwd_at(rp, reinterpret_cast<uint16_t*>(packed + kOffBwd), raw, (int64_t)blockIdx.x * 256 + threadIdx.x);
+// stage 2, block `bid`.  scales null: the image's own (stage 1 wrote them into the raw table); else
+// the given [5 scl | 5 inv], which block 0 also copies into the raw table (the forward kernels read
+// the inverses there) -- no thread of this launch reads the table's scale entries then
+__device__ __forceinline__ void pack_stage2_block(const PackStage2& a, const int bid) {
+  float* raw = a.packed + kOffRaw;
+  const float* scl = a.scales ? a.scales : raw + kRawScl;
+  if (a.scales && bid == 0 && threadIdx.x < 10)
+    raw[(threadIdx.x < 5 ? kRawScl : kRawInv - 5) + threadIdx.x] = a.scales[threadIdx.x];
+  if (bid >= a.nb_bwd + a.nb16)  // the 16-point-wave forward image (after the raw table)
+    pack16w_at(a.rp, reinterpret_cast<uint16_t*>(a.packed + kOffW16), scl, (bid - a.nb_bwd - a.nb16) * 256 + threadIdx.x);
+  else if (bid < a.nb_bwd)
+    pack16_bwd_at(a.rp, reinterpret_cast<uint16_t*>(a.packed + kOffBwd), scl, (int64_t)bid * 256 + threadIdx.x);
   else
-    pack16_at(rp, reinterpret_cast<uint16_t*>(packed + kOffBf2), reinterpret_cast<uint16_t*>(packed + kOffBf1),
-              reinterpret_cast<uint16_t*>(packed + kOffH2), raw,
-              base16 + (int64_t)(blockIdx.x - nb_bwd) * 256 + threadIdx.x);
+    pack16_at(a.rp, reinterpret_cast<uint16_t*>(a.packed + kOffBf2), reinterpret_cast<uint16_t*>(a.packed + kOffBf1),
+              reinterpret_cast<uint16_t*>(a.packed + kOffH2), raw, scl,
+              a.base16 + (int64_t)(bid - a.nb_bwd) * 256 + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void k_pack_stage2(PackStage2 a) { pack_stage2_block(a, (int)blockIdx.x); }
+
+// The head of a captured Mapper iteration as ONE launch: blocks [0, nsamp) are the window sampler's
+// (window_sample.h; its far-clamp ticket counts those blocks alone), the rest pack stage 2 with the
+// given scales.  The two read nothing of each other's.
+__global__ __launch_bounds__(256) void k_sample_pack(WindowSampleArgs ws, int nsamp, PackStage2 a) {
+  if ((int)blockIdx.x < nsamp) window_sample_block(ws, (int)blockIdx.x, nsamp);
+  else pack_stage2_block(a, (int)blockIdx.x - nsamp);
+}
+
+static PackStage2 pack_stage2_args(const RawParams& rp, float* packed, const float* scales, int flags, int* blocks) {
+  const int nb_bwd = (int)((kBwdBytes / 2 + 255) / 256);
+  constexpr int64_t n2 = bf_main_bytes(2) / 2, n1 = bf_main_bytes(1) / 2;
+  const int64_t n16 = 2 * n2 + n1 + kRawWo + 4 * kHidden;
+  const int64_t base16 = (flags & PNR_PACK_F16X3_ONLY) ? n2 + n1 : 0;  // from the f16x3 main image on
+  const int nb16 = (int)((n16 - base16 + 255) / 256);
+  const int nbw = (int)((kW16Bytes / 2 + 255) / 256);
+  *blocks = nb_bwd + nb16 + nbw;
+  return PackStage2{rp, packed, scales, nb_bwd, nb16, base16};
 }
 
 int launch_pack_all(const RawParams& rp, float* packed, hipStream_t st, int flags) {
@@ -264,13 +291,32 @@ int launch_pack_all(const RawParams& rp, float* packed, hipStream_t st, int flag
   const int nscale = 5;
   const int nimg = (flags & PNR_PACK_F16X3_ONLY) ? 0 : (int)std::min<int64_t>(kPack1Blocks, (kPackedFloats + 1023) / 1024);
   hipLaunchKernelGGL(k_pack_stage1, dim3(nscale + nimg), dim3(1024), 0, st, sa, rp, packed, nscale);
-  const int nb_bwd = (int)((kBwdBytes / 2 + 255) / 256);
-  constexpr int64_t n2 = bf_main_bytes(2) / 2, n1 = bf_main_bytes(1) / 2;
-  const int64_t n16 = 2 * n2 + n1 + kRawWo + 4 * kHidden;
-  const int64_t base16 = (flags & PNR_PACK_F16X3_ONLY) ? n2 + n1 : 0;  // from the f16x3 main image on
-  const int nb16 = (int)((n16 - base16 + 255) / 256);
-  const int nbw = (int)((kW16Bytes / 2 + 255) / 256);
-  hipLaunchKernelGGL(k_pack_stage2, dim3(nb_bwd + nb16 + nbw), dim3(256), 0, st, rp, packed, nb_bwd, nb16, base16);
+  int nb = 0;
+  const PackStage2 a = pack_stage2_args(rp, packed, nullptr, flags, &nb);
+  hipLaunchKernelGGL(k_pack_stage2, dim3(nb), dim3(256), 0, st, a);
+  return hip_status(hipGetLastError());
+}
+
+// PNR_PACK_F16X3_ONLY with the scales given: stage 2 alone
+int launch_pack_scaled(const RawParams& rp, float* packed, const float* scales, hipStream_t st) {
+  int nb = 0;
+  const PackStage2 a = pack_stage2_args(rp, packed, scales, PNR_PACK_F16X3_ONLY, &nb);
+  hipLaunchKernelGGL(k_pack_stage2, dim3(nb), dim3(256), 0, st, a);
+  return hip_status(hipGetLastError());
+}
+
+// the window sampler and that pack in one launch
+int launch_sample_pack(uint64_t seed, void* state, int64_t n, int64_t per_frame, int H, int W, float fx, float fy,
+                       float cx, float cy, const float* c2w, const float* depth, const float* color, int S, float* ro,
+                       float* rd, float* gd, float* gc, float* t_rand, int64_t* idx, float* far_out,
+                       const RawParams& rp, float* packed, const float* scales, hipStream_t st) {
+  const WindowSampleArgs ws = window_sample_args(seed, state, n, per_frame, H, W, fx, fy, cx, cy, c2w, depth, color, S,
+                                                 ro, rd, gd, gc, t_rand, idx, far_out);
+  if (ws.n <= 0) return launch_pack_scaled(rp, packed, scales, st);
+  int nb = 0;
+  const PackStage2 a = pack_stage2_args(rp, packed, scales, PNR_PACK_F16X3_ONLY, &nb);
+  const int nsamp = window_sample_blocks(ws.n, ws.S);
+  hipLaunchKernelGGL(k_sample_pack, dim3(nsamp + nb), dim3(256), 0, st, ws, nsamp, a);
   return hip_status(hipGetLastError());
 }
 

@@ -511,7 +511,9 @@ __global__ __launch_bounds__(64 * NW, 1) void k_mlp_fwd16w(BfFwdArgs a, int mode
   using G = W16Geo;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int lane = threadIdx.x & 63, w = wave_id();
-  const int64_t ntiles = (a.P + 16 * NW - 1) / (16 * NW);
+  // a saving forward covers its save rows' padding to 128 (zero rows: the weight-gradient GEMMs read whole
+  // 128-row tiles), also where a 64-point tile (NW 4) holds nothing but padding
+  const int64_t ntiles = SV != 0 ? ((a.P + 127) / 128) * (8 / NW) : (a.P + 16 * NW - 1) / (16 * NW);
   if (SV == 1 && mode == kMapRows) {  // (training only: launch_fwd16w refuses kMapRows otherwise)
     // the map pass's launch-A rows (map_row_point, k_map_pts's arithmetic) of this workgroup's tiles
     // into the x4 rows (src.pts, the x save), by the lanes that load them below (every lane group

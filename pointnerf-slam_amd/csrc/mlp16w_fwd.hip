@@ -26,7 +26,7 @@ int launch_fwd16w(int mode, hipStream_t st, const BfFwdArgs& a, int save, const 
   const int64_t ncu = device_cu_count();
   const int64_t t128 = (a.P + 127) / 128;
   if (nw4_ok && save != 2 && 2 * t128 <= ncu) {
-    const dim3 grid((unsigned)((a.P + 63) / 64));
+    const dim3 grid((unsigned)(save == 0 ? (a.P + 63) / 64 : 2 * t128));  // saves: the padding's tile too
     return save == 0 ? launch16w_sv<0, 4>(mode, grid, st, a, mr) : launch16w_sv<1, 4>(mode, grid, st, a, mr);
   }
   const dim3 grid((unsigned)(t128 < ncu ? t128 : ncu));

@@ -269,6 +269,13 @@ int launch_mlp_bwd_bf(const float* packed, const BwdArgs& a, int64_t P, hipStrea
 int launch_pack(const RawParams& rp, float* packed, hipStream_t st);
 // every image (fp32, 16-bit forward, delta chain, raw table) in two launches (mlp16_pack.hip)
 int launch_pack_all(const RawParams& rp, float* packed, hipStream_t st, int flags = 0);  // PNR_PACK_* flags
+// PNR_PACK_F16X3_ONLY with given scales ([5 scl | 5 inv], device): the images' launch alone
+int launch_pack_scaled(const RawParams& rp, float* packed, const float* scales, hipStream_t st);
+// that pack and the window sampler (launch_window_sample's arguments) as one launch
+int launch_sample_pack(uint64_t seed, void* state, int64_t n, int64_t per_frame, int H, int W, float fx, float fy,
+                       float cx, float cy, const float* c2w, const float* depth, const float* color, int S, float* ro,
+                       float* rd, float* gd, float* gc, float* t_rand, int64_t* idx, float* far_out,
+                       const RawParams& rp, float* packed, const float* scales, hipStream_t st);
 // float offset of Wo [4][256] fp32 in the packed buffer (the raw table's copy, mlp16.h kRawWo)
 int64_t packed_raw_wo_offset();
 int64_t packed_raw_fb_offset();  // the raw table's Fourier B [3][96] (f16x3 path: no fp32 image)
@@ -462,8 +469,31 @@ struct ReduceJob {
   int64_t bias_floats() const { return (int64_t)nwg * nr; }
 };
 constexpr int kMaxReduceJobs = 12;
-// every job's reduction in ONE launch (blocks of a job follow the previous job's)
-int launch_part_reduce_multi(const ReduceJob* jobs, int n, hipStream_t st);
+// The fused tail of a Mapper step (k_reduce_adam_multi): Adam on the flat buffers the reduced
+// gradients live in, and the f16 images' weight scales of the updated tensors.  `scales` is a zeroed
+// area of kStepTailFloats floats: [5 scl | 5 inv | pad | 5 x kStepTailSlots 8-B block-maximum slots |
+// kStepTailGroups ticket counters, 32 floats apart | two entries of Adam bias corrections, by step parity].
+constexpr int kStepTailSlots = 256;   // blocks per scaled tensor (a 256 x 256 tensor at 256 elements each)
+constexpr int kStepTailSlotOff = 16;  // floats ahead of the slots
+constexpr int kStepTailGroups = 32;   // ticket groups of 32 blocks: grids up to 1,024 blocks
+constexpr int kStepTailCntOff = kStepTailSlotOff + 2 * 5 * kStepTailSlots;
+// entry (8 floats): {step + 1 it is for, step_size, bc2_sqrt, lr, beta1, beta2}
+constexpr int kStepTailCoefOff = kStepTailCntOff + 32 * kStepTailGroups;
+constexpr int64_t kStepTailFloats = kStepTailCoefOff + 16;
+struct AdamTail {
+  float* p;        // flat parameters
+  const float* g;  // flat gradients: every reduced gradient lies in [g, g + n)
+  float* m;        // moments of the segment [seg_off, seg_off + n)
+  float* v;
+  int64_t n, seg_off;
+  float lr, beta1, beta2, eps;
+  int32_t* step2;     // {completed steps, ticket 0}, as pnr_adam_multi_dev
+  float* scales;      // kStepTailFloats
+  const float* w[5];  // gradient bases of the scaled tensors W0..W3, Wo (filled by the caller from grads)
+};
+bool part_reduce_vec_enabled();
+// every job's reduction in ONE launch (blocks of a job follow the previous job's); tail: fused with Adam
+int launch_part_reduce_multi(const ReduceJob* jobs, int n, hipStream_t st, const AdamTail* tail = nullptr);
 int launch_wgrad(int kind, const float* A, int ma, const float* B, int nb, int64_t K, float* C, int64_t ldc,
                  float* bias, float* part, float* part_bias, hipStream_t st);
 // split precisions (wgrad16.hip): kWgradHidden / kWgradFirst / kWgradFc as f16x3 GEMMs on fp32

@@ -20,6 +20,8 @@
 
 #include <algorithm>
 
+#include "adam.h"
+#include "window_sample.h"
 #include "pnr_internal.h"
 
 #pragma clang fp contract(off)
@@ -39,14 +41,6 @@ __device__ __forceinline__ float ray_norm(const float* d) {
 // to out[1..], then one block reduces them into out[0] (the workspace slot holds 64 floats).  NaN
 // propagates (torch.max).
 constexpr int kGtParts = 63;
-__device__ __forceinline__ float max_nanf(float m, float v) { return (v > m || v != v) ? v : m; }
-__device__ __forceinline__ float block_max_256(float m, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max_nanf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  return max_nanf(max_nanf(red[0], red[1]), max_nanf(red[2], red[3]));
-}
 __global__ __launch_bounds__(256) void k_gt_max_part(const float* __restrict__ gt, int64_t n, float* __restrict__ out) {
   __shared__ float red[4];
   float m = -INFINITY;
@@ -982,18 +976,6 @@ __global__ __launch_bounds__(256) void k_fine_loss_w(pnr_render_params prm, cons
 }
 
 // ---------------------------------------------------------------------------------------------
-// rays: dirs = [(i-cx)/fx, -(j-cy)/fy, -1]; rays_d = sum(dirs * c2w[:3,:3], -1); rays_o = c2w[:3,3]
-__device__ __forceinline__ void make_ray(float i, float j, float fx, float fy, float cx, float cy,
-                                         const float* __restrict__ c2w, int ld, float* o, float* d) {
-  const float dx = (i - cx) / fx, dy = -((j - cy) / fy), dzv = -1.f;
-  for (int r = 0; r < 3; ++r) {
-    // torch.sum over the last dim of 3 products: ((a0 + a1) + a2), products rounded
-    const float p0 = dx * c2w[r * ld + 0], p1 = dy * c2w[r * ld + 1], p2 = dzv * c2w[r * ld + 2];
-    d[r] = (p0 + p1) + p2;
-    o[r] = c2w[r * ld + 3];
-  }
-}
-
 __global__ void k_get_rays(int H, int W, float fx, float fy, float cx, float cy, const float* __restrict__ c2w,
                            float* __restrict__ ro, float* __restrict__ rd) {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1034,86 +1016,8 @@ __global__ void k_window_rays(const int64_t* __restrict__ idx, int64_t n, int64_
   gc[k * 3 + 2] = color[q * 3 + 2];
 }
 
-// A mapping iteration's whole window batch in ONE launch, drawn on the device: the uniform pixels
-// (torch.randint(H*W) per ray in Mapper.py:560-606's get_samples), the regulation jitter t_rand
-// (torch.rand, Renderer.py:293), the rays and gt of k_window_rays, and the batch far clamp
-// max(1.2 gt) (k_gt_max, Renderer.py:112) -- in place of randint + rand (+ the two seed / offset
-// fills torch's RNG records in a captured graph) + the gt max.  The draws are a counter-based hash
-// (splitmix64 finaliser of seed, batch and draw index), not torch's Philox stream: the same
-// distribution, a different sequence.  The state holds the batch counter (advanced by the block
-// that takes the last ticket, so a captured graph draws a fresh batch per replay), the ticket and
-// the per-block maxima.
-constexpr int kSampleParts = 64;
-struct SampleState {
-  int64_t batch;
-  uint32_t ticket;
-  uint32_t pad;
-  uint64_t part[kSampleParts];  // per-block gt maxima (float bits), written and read by 8-B atomics
-};
-static_assert(sizeof(SampleState) == 16 + 8 * kSampleParts, "sampler state layout");
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__global__ __launch_bounds__(256) void k_window_sample(uint64_t seed, SampleState* __restrict__ stt, int64_t n,
-                                                       int64_t per_frame, int64_t hw, int W, float fx, float fy,
-                                                       float cx, float cy, const float* __restrict__ c2w,
-                                                       const float* __restrict__ depth,
-                                                       const float* __restrict__ color, int S, float* __restrict__ ro,
-                                                       float* __restrict__ rd, float* __restrict__ gd,
-                                                       float* __restrict__ gc, float* __restrict__ t_rand,
-                                                       int64_t* __restrict__ idx_out, float* __restrict__ far_out) {
-  __shared__ float red[4];
-  __shared__ uint32_t last;
-  const int64_t batch = stt->batch;
-  const uint64_t base = mix64(seed + (uint64_t)batch * 0x9E3779B97F4A7C15ull);
-  // blocks [0, nbr) draw the rays (and their gt maxima, part[0..nbr)); the others draw the jitter,
-  // one value per thread (a thread per ray drawing its 32 values serially was the launch's latency)
-  const int nbr = (int)(n < (int64_t)kSampleParts * 256 ? (n + 255) / 256 : kSampleParts);
-  float m = -INFINITY;
-  if ((int)blockIdx.x < nbr) {
-    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)nbr * 256) {
-      const int64_t f = k / per_frame;
-      const uint64_t r = mix64(base + (uint64_t)k * 0xD1B54A32D192ED03ull);
-      const int64_t pix = (int64_t)(((r >> 32) * (uint64_t)hw) >> 32);  // uniform in [0, hw) (hw < 2^32)
-      if (idx_out) idx_out[k] = pix;
-      make_ray((float)(pix % W), (float)(pix / W), fx, fy, cx, cy, c2w + f * 16, 4, ro + k * 3, rd + k * 3);
-      const int64_t q = f * hw + pix;
-      const float d = depth[q];
-      gd[k] = d;
-      gc[k * 3 + 0] = color[q * 3 + 0];
-      gc[k * 3 + 1] = color[q * 3 + 1];
-      gc[k * 3 + 2] = color[q * 3 + 2];
-      m = max_nanf(m, d * 1.2f);
-    }
-  } else {
-    const int64_t ns = n * S, stride = (int64_t)(gridDim.x - nbr) * 256;
-    for (int64_t e = (int64_t)(blockIdx.x - nbr) * 256 + threadIdx.x; e < ns; e += stride) {
-      // 24-bit uniforms in [0, 1), like torch.rand's float32: value (k, s) is draw n + k S + s
-      const uint64_t u = mix64(base + (uint64_t)(n + e) * 0xD1B54A32D192ED03ull);
-      t_rand[e] = (float)(uint32_t)(u >> 40) * 0x1p-24f;
-    }
-  }
-  m = block_max_256(m, red);
-  // ticket hand-off as k_map_loss (8-B agent atomics both sides); the last block reduces the maxima
-  // and advances the batch
-  if (threadIdx.x == 0) {
-    if ((int)blockIdx.x < nbr) atomicExch(stt->part + blockIdx.x, (unsigned long long)__float_as_uint(m));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t t = atomicAdd(&stt->ticket, 1u);
-    last = t == gridDim.x - 1 ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!last) return;
-  __shared__ float red2[4];
-  const float v = block_max_256(
-      (int)threadIdx.x < nbr ? __uint_as_float((uint32_t)atomicAdd(stt->part + threadIdx.x, 0ull)) : -INFINITY, red2);
-  if (threadIdx.x == 0) {
-    if (far_out) far_out[0] = v;
-    stt->batch = batch + 1;
-    stt->ticket = 0u;
-  }
+__global__ __launch_bounds__(256) void k_window_sample(WindowSampleArgs a) {
+  window_sample_block(a, (int)blockIdx.x, (int)gridDim.x);  // window_sample.h
 }
 
 // torch.optim.Adam (amsgrad=False, weight_decay=0), single-tensor semantics
@@ -1172,10 +1076,7 @@ __global__ __launch_bounds__(256) void k_adam_multi(float* __restrict__ p, const
   const int64_t i0 = (int64_t)((int)blockIdx.x - S.first[q]) * 256 + threadIdx.x;
   const int64_t stride = (int64_t)(S.first[q + 1] - S.first[q]) * 256;
   const int32_t step = step2[0];
-  const double t = (double)(step + 1);
-  const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
-  const float step_size = (float)((double)S.lr[q] / bc1);
-  const float bc2_sqrt = (float)sqrt(bc2);
+  const AdamCoef coef = adam_coef(step, S.lr[q], beta1, beta2);
   // four elements in flight per thread (loads first), so the grid stays small without a serial
   // chain of dependent loads per thread
   const int64_t nq = S.n[q], off = S.off[q];
@@ -1196,12 +1097,9 @@ __global__ __launch_bounds__(256) void k_adam_multi(float* __restrict__ p, const
     for (int u = 0; u < 4; ++u) {
       const int64_t i = b + u * stride;
       if (i < nq) {
-        const float mn = mi[u] + (1.f - beta1) * (gi[u] - mi[u]);
-        const float vn = vi[u] * beta2 + (1.f - beta2) * gi[u] * gi[u];
-        mq[i] = mn;
-        vq[i] = vn;
-        const float denom = sqrtf(vn) / bc2_sqrt + eps;
-        const float pn = pi[u] + (-step_size) * (mn / denom);
+        const float pn = adam_update(gi[u], mi[u], vi[u], pi[u], beta1, beta2, eps, coef);  // adam.h
+        mq[i] = mi[u];
+        vq[i] = vi[u];
         p[off + i] = pn;
         if (hq) hq[i] = __builtin_bit_cast(uint16_t, (_Float16)pn);  // RNE, as torch's float16 copy
       }
@@ -1433,11 +1331,9 @@ int launch_window_sample(uint64_t seed, void* state, int64_t n, int64_t per_fram
                          float* ro, float* rd, float* gd, float* gc, float* t_rand, int64_t* idx, float* far_out,
                          hipStream_t st) {
   if (n <= 0) return 0;
-  const int64_t nbr = std::min<int64_t>(kSampleParts, nblk(n, 256));                  // ray blocks
-  const int64_t nbj = std::min<int64_t>(192, nblk(n * (S > 0 ? S : 0), 1024));      // jitter blocks (4 per thread)
-  const int64_t nb = nbr + nbj;
-  hipLaunchKernelGGL(k_window_sample, dim3((unsigned)nb), dim3(256), 0, st, seed, (SampleState*)state, n, per_frame,
-                     (int64_t)H * W, W, fx, fy, cx, cy, c2w, depth, color, S, ro, rd, gd, gc, t_rand, idx, far_out);
+  const WindowSampleArgs a = window_sample_args(seed, state, n, per_frame, H, W, fx, fy, cx, cy, c2w, depth, color, S,
+                                                ro, rd, gd, gc, t_rand, idx, far_out);
+  hipLaunchKernelGGL(k_window_sample, dim3((unsigned)window_sample_blocks(n, S)), dim3(256), 0, st, a);
   return hip_status(hipGetLastError());
 }
 int launch_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,

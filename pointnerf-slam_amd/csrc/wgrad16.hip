@@ -39,6 +39,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "adam.h"
 #include "mlp16.h"
 
 namespace pnr {
@@ -665,12 +666,30 @@ struct ReduceJobs {
   int n;
 };
 
+// The Adam tail of k_reduce_adam_multi (device view of AdamTail): job q's gradients are the scaled
+// weight tensor tens[q] (0..3: W0..W3, 4: Wo) or none (-1: biases ride with their job, B has none)
+struct AdamTailDev {
+  AdamTail t;
+  int tens[kMaxReduceJobs];
+  int nblk[5];  // main (non-bias) blocks of each scaled tensor = its used slots
+};
+
 // every job of a backward chunk in one launch: block b belongs to the job whose block range holds it,
 // then the same fixed-order reduction as k_part_reduce.  A job whose partial rows are whole float4s
 // (nr pw and pw multiples of 4, 16-B aligned regions: every GEMM job) runs 4 consecutive elements per
 // lane, 256 per block -- the same chains and order per element, a quarter of the blocks and load
 // instructions (the partial tiles are the launch's bytes: 55 MB at the room0 batch)
-__global__ __launch_bounds__(64 * kRedWaves) void k_part_reduce_multi(ReduceJobs J) {
+//
+// ADAM (k_reduce_adam_multi): the owner lane of an element also takes its Adam step -- the gradient it
+// has just formed never comes back from memory, and m / v / p are loaded ahead of the partial loop.  The
+// element's flat index is its gradient address minus the flat gradient base (p by that index, m / v by
+// it minus the segment offset).  A block of a scaled weight tensor publishes max|p'| of its elements to
+// a slot of its own (8-B agent exchange, s_waitcnt, then the ticket: k_window_sample's hand-off); the
+// block that takes the last (top-level) ticket folds the slots per tensor into the ten scale floats of the next
+// pack (wscale_from_max, as wscale_block), advances the step and zeroes the ticket.  Every block
+// reads the step before its ticket.  A max is exact in any order: the bits are wscale_block's.
+template <bool ADAM>
+__device__ __forceinline__ void reduce_multi_body(const ReduceJobs& J, const AdamTailDev* __restrict__ T) {
   __shared__ float4 red[kRedWaves][64];
   int q = 0;
   while (q + 1 < J.n && (int)blockIdx.x >= J.first[q + 1]) ++q;
@@ -678,13 +697,81 @@ __global__ __launch_bounds__(64 * kRedWaves) void k_part_reduce_multi(ReduceJobs
   const int lane = threadIdx.x & 63, v = threadIdx.x >> 6;
   const int64_t E = (int64_t)jb.nr * jb.pw;
   const int64_t blk = (int64_t)blockIdx.x - J.first[q];
-  if (J.vec[q]) {
-    const int64_t nmain = (E + 255) / 256;
-    const bool is_bias = blk >= nmain;
-    const int64_t e = (is_bias ? blk - nmain : blk) * 256 + 4 * lane;
-    const float* src = is_bias ? jb.pbias : jb.part;
-    const int64_t stride = is_bias ? jb.nr : E;
-    const bool any = is_bias ? (jb.bias != nullptr && e < jb.nr) : e < E;  // all 4 in range (E, nr: x 4)
+  const int nvec = J.vec[q] ? 4 : 1;
+  const int64_t epb = 64 * nvec;
+  const int64_t nmain = (E + epb - 1) / epb;
+  const bool is_bias = blk >= nmain;
+  const int64_t e = (is_bias ? blk - nmain : blk) * epb + nvec * lane;
+  const float* src = is_bias ? jb.pbias : jb.part;
+  const int64_t stride = is_bias ? jb.nr : E;
+  // vec: all 4 in range (E, nr: x 4), padding columns skipped per element below
+  const bool any = is_bias ? (jb.bias != nullptr && e < jb.nr) : e < E;
+  // the owner lane's destinations, and (ADAM) its m / v / p in flight under the partial loop
+  float* dst[4] = {nullptr, nullptr, nullptr, nullptr};
+  float am[4], av[4], ap[4];
+  int64_t ai[4];
+  int32_t step = 0;
+  AdamCoef coef{};
+  float cc[6], cc2[6];  // (ADAM) the two bias-correction entries (by step parity) the previous launches left
+  if (v == 0) {
+    if (any) {
+      // (32-bit row / column when the job allows: eight 64-bit divisions ahead of the loop held wave 0,
+      // and with it the block's barrier, back)
+      const bool small = E < (1LL << 31);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int64_t ek = e + k;
+        if (k >= nvec) continue;
+        int64_t row = 0, col = 0;
+        if (!is_bias) {
+          if (small) {
+            row = (uint32_t)ek / (uint32_t)jb.pw;
+            col = (uint32_t)ek - (uint32_t)row * (uint32_t)jb.pw;
+          } else {
+            row = ek / jb.pw;
+            col = ek % jb.pw;
+          }
+          if ((int)col >= jb.nb) continue;  // padding columns (W0: 93 of 96)
+        }
+        dst[k] = is_bias ? jb.bias + ek : jb.C + row * jb.ldc + col;
+        if constexpr (ADAM) {
+          ai[k] = dst[k] - T->t.g;
+          am[k] = T->t.m[ai[k] - T->t.seg_off];
+          av[k] = T->t.v[ai[k] - T->t.seg_off];
+          ap[k] = T->t.p[ai[k]];
+        }
+      }
+    }
+    if constexpr (ADAM) {
+      // the step and both bias-correction entries: loaded here, first used behind the barrier (a use
+      // ahead of the partial loop made wave 0 -- and so every wave of the block, at the barrier -- wait
+      // a memory round trip before its first partial load: 19.5 against 13.4 us for the whole launch)
+      step = T->t.step2[0];
+      const float* c0 = T->t.scales + kStepTailCoefOff;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) cc[i] = c0[i];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) cc2[i] = c0[8 + i];
+    }
+  }
+  if constexpr (ADAM) {
+    // the next step's bias corrections, by a wave off every critical path (block 0's wave 1), into the
+    // entry this launch does not use.  Its read of the step comes before the step can advance: the value
+    // is consumed (the pow, the stores below) before this wave reaches the barrier, the block's ticket
+    // follows that barrier, and the step advances only after every block's ticket.
+    if (blockIdx.x == 0 && v == 1 && lane == 0) {
+      const int32_t st = T->t.step2[0];
+      float* cc = T->t.scales + kStepTailCoefOff + 8 * ((st + 1) & 1);
+      const AdamCoef nx = adam_coef(st + 1, T->t.lr, T->t.beta1, T->t.beta2);
+      cc[0] = __int_as_float(st + 2);
+      cc[1] = nx.step_size;
+      cc[2] = nx.bc2_sqrt;
+      cc[3] = T->t.lr;
+      cc[4] = T->t.beta1;
+      cc[5] = T->t.beta2;
+    }
+  }
+  if (nvec == 4) {
     float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
     if (any) {
       int g = v;
@@ -701,57 +788,139 @@ __global__ __launch_bounds__(64 * kRedWaves) void k_part_reduce_multi(ReduceJobs
       }
     }
     red[v][lane] = make_float4(s0.x + s1.x, s0.y + s1.y, s0.z + s1.z, s0.w + s1.w);
-    __syncthreads();
-    if (v == 0 && any) {
-      float4 t = red[0][lane];
+  } else {
+    float s0 = 0.f, s1 = 0.f;
+    if (any && (is_bias || (int)(e % jb.pw) < jb.nb)) {
+      int g = v;
+#pragma unroll 4
+      for (; g + kRedWaves < jb.nwg; g += 2 * kRedWaves) {
+        s0 += src[(int64_t)g * stride + e];
+        s1 += src[(int64_t)(g + kRedWaves) * stride + e];
+      }
+      if (g < jb.nwg) s0 += src[(int64_t)g * stride + e];
+    }
+    red[v][lane].x = s0 + s1;
+  }
+  __syncthreads();
+  if (v != 0) return;
+  float mx = 0.f;  // max |p'| of this lane's elements (ADAM, scaled tensors)
+  if constexpr (ADAM) {
+    // the bias corrections: left by the previous launch (two double pow per block were this wave's
+    // longest dependent chain), else computed here -- the same function of the same inputs.  `step`
+    // is consumed here, ahead of the block's ticket.
+    if (step & 1) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) cc[i] = cc2[i];
+    }
+    if (__float_as_int(cc[0]) == step + 1 && cc[3] == T->t.lr && cc[4] == T->t.beta1 && cc[5] == T->t.beta2)
+      coef = AdamCoef{cc[1], cc[2]};
+    else
+      coef = adam_coef(step, T->t.lr, T->t.beta1, T->t.beta2);
+  }
+  float pn[4], gn[4];
+  if (any) {
+    float4 t = red[0][lane];
+    if (nvec == 4) {
 #pragma unroll
       for (int i = 1; i < kRedWaves; ++i) {
         const float4 u = red[i][lane];
         t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
       }
-      const float sv[4] = {t.x, t.y, t.z, t.w};
+    } else {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int64_t ek = e + k;
-        if (!is_bias && (int)(ek % jb.pw) >= jb.nb) continue;  // padding columns (W0: 93 of 96)
-        float* dst = is_bias ? jb.bias + ek : jb.C + (ek / jb.pw) * jb.ldc + ek % jb.pw;
-        *dst = (jb.overwrite ? 0.f : *dst) + sv[k];
+      for (int i = 1; i < kRedWaves; ++i) t.x += red[i][lane].x;
+    }
+    const float sv[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (dst[k] == nullptr) continue;
+      const float g = (jb.overwrite ? 0.f : *dst[k]) + sv[k];
+      if constexpr (ADAM) {  // (g, m, v, p go out after the ticket: their stores' latency stays off the hand-off)
+        gn[k] = g;
+        pn[k] = adam_update(g, am[k], av[k], ap[k], T->t.beta1, T->t.beta2, T->t.eps, coef);  // adam.h
+        mx = fmaxf(mx, fabsf(pn[k]));
+      } else {
+        *dst[k] = g;
       }
     }
-    return;
   }
-  const int64_t nmain = (E + 63) / 64;
-  const bool is_bias = blk >= nmain;
-  const int64_t e = (is_bias ? blk - nmain : blk) * 64 + lane;
-  const float* src = is_bias ? jb.pbias : jb.part;
-  const int64_t stride = is_bias ? jb.nr : E;
-  const bool ok = is_bias ? (jb.bias != nullptr && e < jb.nr) : (e < E && (int)(e % jb.pw) < jb.nb);
-  float s0 = 0.f, s1 = 0.f;
-  if (ok) {
-    int g = v;
-#pragma unroll 4
-    for (; g + kRedWaves < jb.nwg; g += 2 * kRedWaves) {
-      s0 += src[(int64_t)g * stride + e];
-      s1 += src[(int64_t)(g + kRedWaves) * stride + e];
-    }
-    if (g < jb.nwg) s0 += src[(int64_t)g * stride + e];
-  }
-  red[v][lane].x = s0 + s1;
-  __syncthreads();
-  if (v == 0 && ok) {
-    float s = red[0][lane].x;
+  if constexpr (ADAM) {
+    const int tn = is_bias ? -1 : T->tens[q];
+    unsigned long long* slots = reinterpret_cast<unsigned long long*>(T->t.scales + kStepTailSlotOff);
 #pragma unroll
-    for (int i = 1; i < kRedWaves; ++i) s += red[i][lane].x;
-    float* dst = is_bias ? jb.bias + e : jb.C + (e / jb.pw) * jb.ldc + e % jb.pw;
-    *dst = (jb.overwrite ? 0.f : *dst) + s;
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    // tickets in two levels: 32 consecutive blocks share a counter of their own (128 B apart), and the
+    // block that takes a group's last ticket takes one of the top counter (step2[1]) -- ~900 tickets on
+    // one address queued for longer than the reduction itself takes
+    uint32_t last = 0;
+    if (lane == 0) {
+      if (tn >= 0) atomicExch(slots + tn * kStepTailSlots + blk, (unsigned long long)__float_as_uint(mx));
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const uint32_t grp = blockIdx.x >> 5, ngrp = (gridDim.x + 31) >> 5;
+      const uint32_t gsize = grp + 1 < ngrp ? 32u : gridDim.x - 32u * grp;
+      uint32_t* cnt = reinterpret_cast<uint32_t*>(T->t.scales + kStepTailCntOff) + 32 * grp;
+      if (atomicAdd(cnt, 1u) == gsize - 1) {
+        *cnt = 0u;  // (every block of the group has taken its ticket: zero for the next launch)
+        last = atomicAdd(reinterpret_cast<uint32_t*>(T->t.step2 + 1), 1u) == ngrp - 1 ? 1u : 0u;
+      }
+    }
+    if (any) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (dst[k] == nullptr) continue;
+        *dst[k] = gn[k];
+        T->t.m[ai[k] - T->t.seg_off] = am[k];
+        T->t.v[ai[k] - T->t.seg_off] = av[k];
+        T->t.p[ai[k]] = pn[k];
+      }
+    }
+    if (!__shfl(last, 0)) return;
+    // the last block: every slot has been published (each block's exchange completed before its ticket)
+    // (all twenty reads in flight before the first is used: one round trip, not five)
+    float a[5][kStepTailSlots / 64];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+#pragma unroll
+      for (int r = 0; r < kStepTailSlots / 64; ++r) {
+        const int k = lane + 64 * r;
+        a[i][r] = k < T->nblk[i] ? __uint_as_float((uint32_t)atomicAdd(slots + i * kStepTailSlots + k, 0ull)) : 0.f;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+      float m = a[i][0];
+#pragma unroll
+      for (int r = 1; r < kStepTailSlots / 64; ++r) m = fmaxf(m, a[i][r]);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+      if (lane == 0) wscale_from_max(m, T->t.scales + i, T->t.scales + 5 + i);
+    }
+    if (lane == 0) {
+      T->t.step2[0] = step + 1;
+      T->t.step2[1] = 0;
+    }
   }
 }
+__global__ __launch_bounds__(64 * kRedWaves) void k_part_reduce_multi(ReduceJobs J) {
+  reduce_multi_body<false>(J, nullptr);
+}
+__global__ __launch_bounds__(64 * kRedWaves) void k_reduce_adam_multi(ReduceJobs J, AdamTailDev T) {
+  reduce_multi_body<true>(J, &T);
+}
 
-int launch_part_reduce_multi(const ReduceJob* jobs, int n, hipStream_t st) {
-  if (n <= 0) return 0;
-  if (n > kMaxReduceJobs) return PNR_E_ARG;
+bool part_reduce_vec_enabled() {
   static const bool vec_ok = !(getenv("PNR_REDUCE_VEC") && getenv("PNR_REDUCE_VEC")[0] == '0');
+  return vec_ok;
+}
+
+// tail non-null: the fused reduce + Adam + scales launch (the caller has checked that the jobs store,
+// that this is the backward's only chunk and that every gradient lies in the tail's flat buffer)
+int launch_part_reduce_multi(const ReduceJob* jobs, int n, hipStream_t st, const AdamTail* tail) {
+  if (n <= 0) return tail ? PNR_E_ARG : 0;
+  if (n > kMaxReduceJobs) return PNR_E_ARG;
+  const bool vec_ok = part_reduce_vec_enabled();
   ReduceJobs J{};
+  AdamTailDev T{};
   int blocks = 0;
   for (int i = 0; i < n; ++i) {
     const ReduceJob& r = jobs[i];
@@ -763,11 +932,29 @@ int launch_part_reduce_multi(const ReduceJob* jobs, int n, hipStream_t st) {
                      (r.bias == nullptr || reinterpret_cast<uintptr_t>(r.pbias) % 16 == 0);
     J.vec[i] = vec ? 1 : 0;
     const int epb = vec ? 256 : 64;
-    blocks += (int)((E + epb - 1) / epb + (r.bias ? (r.nr + epb - 1) / epb : 0));
+    const int nmain = (int)((E + epb - 1) / epb);
+    blocks += nmain + (int)(r.bias ? (r.nr + epb - 1) / epb : 0);
+    if (tail) {
+      T.tens[i] = -1;
+      for (int k = 0; k < 5; ++k)
+        if (r.C == tail->w[k]) T.tens[i] = k;
+      if (T.tens[i] >= 0) {
+        if (nmain > kStepTailSlots || T.nblk[T.tens[i]] != 0 || !r.overwrite) return PNR_E_ARG;
+        T.nblk[T.tens[i]] = nmain;
+      }
+    }
   }
   J.first[n] = blocks;
   J.n = n;
-  hipLaunchKernelGGL(k_part_reduce_multi, dim3((unsigned)blocks), dim3(64 * kRedWaves), 0, st, J);
+  if (tail) {
+    if (blocks > 32 * kStepTailGroups) return PNR_E_ARG;
+    for (int k = 0; k < 5; ++k)
+      if (T.nblk[k] == 0) return PNR_E_ARG;  // every scaled tensor has its job
+    T.t = *tail;
+    hipLaunchKernelGGL(k_reduce_adam_multi, dim3((unsigned)blocks), dim3(64 * kRedWaves), 0, st, J, T);
+  } else {
+    hipLaunchKernelGGL(k_part_reduce_multi, dim3((unsigned)blocks), dim3(64 * kRedWaves), 0, st, J);
+  }
   return hip_status(hipGetLastError());
 }
 

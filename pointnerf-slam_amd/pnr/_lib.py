@@ -65,6 +65,15 @@ class RenderParams(ctypes.Structure):
     ]
 
 
+class AdamTail(ctypes.Structure):
+    """Mirror of `pnr_adam_tail` (include/pnr.h)."""
+    _fields_ = [
+        ('p', c_void_p), ('g', c_void_p), ('m', c_void_p), ('v', c_void_p), ('n', c_int64),
+        ('lr', c_float), ('beta1', c_float), ('beta2', c_float), ('eps', c_float),
+        ('step2', c_void_p), ('scales', c_void_p),
+    ]
+
+
 PtrArray = c_void_p * N_PARAMS
 FcPtrArray = c_void_p * N_FC_PARAMS
 PPoints = ctypes.POINTER(Points)
@@ -109,6 +118,16 @@ _SIGS = {
     'pnr_map_step': (ctypes.c_int, [ctypes.POINTER(RenderParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p, c_size_t, c_void_p, c_void_p]),
+    'pnr_step_tail_floats': (c_size_t, []),
+    'pnr_map_step_adam': (ctypes.c_int, [ctypes.POINTER(RenderParams), c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                         c_size_t, c_void_p, c_size_t, c_void_p, ctypes.POINTER(AdamTail),
+                                         ctypes.POINTER(c_int32), c_void_p]),
+    'pnr_mlp_pack_scaled': (ctypes.c_int, [PtrArray, c_void_p, c_void_p, c_void_p]),
+    'pnr_window_sample_pack': (ctypes.c_int, [ctypes.c_uint64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_float,
+                                              c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int32,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              PtrArray, c_void_p, c_void_p, c_void_p]),
     'pnr_get_rays': (ctypes.c_int, [c_int32, c_int32, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
     'pnr_rays_from_uv': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_void_p,

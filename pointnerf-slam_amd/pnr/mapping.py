@@ -133,6 +133,9 @@ class MapStep:
     OVERLAP_MAX_RAYS = 32768
     # the fused path as one pnr_map_step call (ABI 13) rather than pnr_map_fwd + pnr_map_loss + pnr_map_bwd
     one_call = True
+    # let the gradient reduction take the Adam step and form the next pack's scales (pnr_map_step_adam)
+    # when the step qualifies (`_wants_tail`); `tail_fused` tells which path the last step took
+    fuse_tail = True
 
     def __init__(self, renderer, decoder, lr=2e-4, w_color_loss=0.05, w_reg=0.0005, ddp=None, points=None,
                  feat_lr=None, overlap='auto', fused=True):
@@ -174,6 +177,8 @@ class MapStep:
         self.side = None   # the side stream and the regulation chain's gradient buffer (same layout
         self.grad2 = None  # as flat.grad) with its views: made on the first overlapped step
         self._views = {'main': self._split(self.flat.grad)}
+        self.tail_fused = False  # the last step ran reduce + Adam + scales as one launch
+        self._tail = None        # (AdamTail descriptor, its scales / hand-off area)
 
     def _loss_ws(self, chain):
         """The pnr_map_loss workspace of a chain's stream (zero-filled once; each call leaves it zero)."""
@@ -197,6 +202,35 @@ class MapStep:
         if self.points is None:
             return views, None, None
         return views[:11], views[11:19], views[19]
+
+    def _wants_tail(self):
+        """The fused tail's conditions on this side of the C call (single GPU, decoder only, the f16x3
+        precision, Adam on the device step counter); pnr_map_step_adam checks the rest."""
+        return (self.fuse_tail and self.fused and self.one_call and self.ddp is None and self.points is None
+                and self.renderer.precision == 'f16x3' and self.opt.step_dev is not None
+                and len(self.opt.segments) == 1 and self.opt.segments[0][:2] == (0, self.flat.numel))
+
+    def _tail_desc(self):
+        """The pnr_adam_tail of this call: built from the optimiser as it stands now (segment 0's learning
+        rate, the betas, eps, the buffers), so a later change of any of them reaches the fused tail as it
+        reaches Adam.step; only the scales / hand-off area is kept from call to call."""
+        o, f = self.opt, self.flat
+        if self._tail is None:
+            self._tail = (None, torch.zeros(_lib.load().pnr_step_tail_floats(), device=f.data.device))
+        area = self._tail[1]
+        m, v = o.mv[0]
+        t = _lib.AdamTail(f.data.data_ptr(), f.grad.data_ptr(), m.data_ptr(), v.data_ptr(), f.numel,
+                          o.segments[0][2], o.b1, o.b2, o.eps, o.step_dev.data_ptr(), area.data_ptr())
+        self._tail = (t, area)
+        return t
+
+    def head_pack(self):
+        """(tensor pointers, image, scales) for a caller that packs in its own launch, when the last step
+        left fresh scales (PackedMLP.adopt); else None."""
+        if not self._wants_tail():
+            return None
+        from .renderer import _decoder_params, _packer
+        return _packer(self.decoder).adopt(_decoder_params(self.decoder))
 
     def _invalidate(self):
         self.decoder._packed.invalidate()
@@ -249,9 +283,16 @@ class MapStep:
             mp = MapPass(r, self.c, self.decoder)
             views = self._views['main']
             if self.one_call:  # pnr_map_step: forward, loss and backward in one C call, fused tail
+                tail = self._tail_desc() if self._wants_tail() else None
                 loss = mp.step(rays_o, rays_d, gt_depth, gt_color, t_rand, self.w_color, self.w_reg,
                                self._loss_ws('main'), views[0], g_fc=views[1], g_feats=views[2],
-                               far_clamp=far_clamp, overwrite=True)
+                               far_clamp=far_clamp, overwrite=True, tail=tail)
+                self.tail_fused = mp.tail_fused
+                if mp.tail_fused:  # Adam ran inside the reduction: the image is stale, its next scales are not
+                    self.opt.step_count += 1
+                    self.opt.wrote_half = False
+                    mp.packer.scales_fresh(mp.feat.params, self._tail[1])
+                    return loss
                 return self._finish(loss)
             d, _, c, sigma = mp.forward(rays_o, rays_d, gt_depth, t_rand, far_clamp=far_clamp)
             loss, g_d, g_c, g_s = map_loss(gt_depth, d, gt_color, c, self.w_color, sigma=sigma, w_reg=self.w_reg,
@@ -284,6 +325,7 @@ class MapStep:
 
     def _finish(self, loss):
         """The gradient exchange (data parallel) and the Adam step."""
+        self.tail_fused = False
         if self.ddp is not None and self.shard:
             self.ddp.allreduce_(self.flat.grad[:self.n_dec])
             self.ddp.reduce_scatter_(self.flat.grad[self.n_dec:])
@@ -323,10 +365,21 @@ class MapGraph:
     clamp is all-reduced and read on the device (far_mode 2), so the step has no host sync; gloo
     collectives cannot be captured.  `warmup` ordinary steps run first on the given batch (torch
     requires work on a side stream before a capture); they are real optimisation steps.
+
+    `carry_scales` (default True): when the step's tail is fused (MapStep.tail_fused: reduce + Adam +
+    weight scales in one launch) the captured iteration repacks the f16x3 weight images from the scales
+    the PREVIOUS iteration's tail left on the device -- no max|W| pass of its own.  Such a graph is valid
+    only while nothing but its own replays moves the decoder weights: after load_state_dict, an eager
+    step through another optimiser path or a manual opt.step(), make a new MapGraph (its warm-up steps
+    bring the scales up to date) instead of replaying this one; Python's "scales fresh" mark cannot
+    reach inside a captured graph.  (An eager MapStep between replays is fine: its fused tail leaves the
+    same area current, and an unfused one is exactly the case above.)  carry_scales=False captures the
+    self-contained form instead: every replay recomputes the scales (the full f16x3 repack, two
+    launches more).
     """
 
     def __init__(self, mstep: MapStep, rays_o=None, rays_d=None, gt_depth=None, gt_color=None, t_rand=None,
-                 warmup=2, batch_fn=None):
+                 warmup=2, batch_fn=None, carry_scales=True):
         """`batch_fn` (optional): a callable producing (rays_o, rays_d, gt_depth, gt_color, t_rand) on
         the device -- e.g. a Mapper iteration's window sampling (WindowSampler) -- captured INTO the
         graph together with the step, so each replay draws a fresh batch (torch's CUDA RNG is
@@ -344,7 +397,13 @@ class MapGraph:
         else:
             dev = batch_fn()[0].device
             self.inputs = None
-            body = lambda: mstep(*batch_fn())  # noqa: E731
+
+            def body():
+                # the window sampler and the stage-2-only repack as ONE launch when the last step left
+                # fresh scales (pnr_window_sample_pack); any other batch_fn or state: separate calls
+                grouped = carry_scales and isinstance(batch_fn, WindowSampler) and batch_fn.device_rng
+                pack = mstep.head_pack() if grouped else None
+                return mstep(*(batch_fn(pack=pack) if pack is not None else batch_fn()))
         mstep.opt.use_device_step()
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -352,7 +411,10 @@ class MapGraph:
             for _ in range(warmup):
                 body()
         torch.cuda.current_stream(dev).wait_stream(side)
-        mstep._invalidate()  # the captured step starts with the weight repack
+        # the captured step starts with the weight repack: in full, or (after a warm-up step whose tail
+        # was fused) from the scales that step -- and then every replay -- leaves
+        if not (mstep.tail_fused and carry_scales):
+            mstep._invalidate()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss = body()
@@ -448,7 +510,8 @@ class WindowSampler:
             dev = self.depth.device
             self.state = torch.zeros(lib.pnr_window_sample_state_bytes(), dtype=torch.uint8, device=dev)
 
-    def __call__(self):
+    def __call__(self, pack=None):
+        """`pack` (MapStep.head_pack()): also run the stage-2-only weight repack in the same launch."""
         F, H, W = self.depth.shape
         dev = self.depth.device
         N = F * self.n
@@ -466,6 +529,16 @@ class WindowSampler:
         t_rand = torch.empty((N, self.n_samples), device=dev)
         self.idx = torch.empty(N, dtype=torch.int64, device=dev)
         far = torch.empty(1, device=dev)
+        if pack is not None:
+            arr, img, scales = pack
+            _lib.check(lib.pnr_window_sample_pack(self.seed, _lib.ptr(self.state), N, self.n, H, W,
+                                                  *[float(v) for v in self.cam], _lib.ptr(self.c2w),
+                                                  _lib.ptr(self.depth), _lib.ptr(self.color), self.n_samples,
+                                                  _lib.ptr(ro), _lib.ptr(rd), _lib.ptr(gd), _lib.ptr(gc),
+                                                  _lib.ptr(t_rand), _lib.ptr(self.idx), _lib.ptr(far), arr,
+                                                  _lib.ptr(img), _lib.ptr(scales), _lib.stream_of(dev)),
+                       'window_sample_pack')
+            return ro, rd, gd, gc, t_rand, far
         _lib.check(lib.pnr_window_sample(self.seed, _lib.ptr(self.state), N, self.n, H, W,
                                          *[float(v) for v in self.cam], _lib.ptr(self.c2w), _lib.ptr(self.depth),
                                          _lib.ptr(self.color), self.n_samples, _lib.ptr(ro), _lib.ptr(rd),

@@ -370,10 +370,13 @@ class MapPass:
         self.ws = self.packed = None
 
     def step(self, rays_o, rays_d, gt_depth, gt_color, t_rand, w_color, w_reg, loss_ws, grads, g_fc=None,
-             g_feats=None, far_clamp=None, overwrite=False):
+             g_feats=None, far_clamp=None, overwrite=False, tail=None):
         """forward + map_loss + backward in ONE C call (pnr_map_step, ABI 13): at batches up to 32,768 rays
         the compositing, the loss and the compositing backward are one fused launch.  Same gradients as
-        the three-call form bit for bit; returns the float64 loss (0-dim, on the device)."""
+        the three-call form bit for bit; returns the float64 loss (0-dim, on the device).
+        `tail` (a _lib.AdamTail): pnr_map_step_adam -- the gradient reduction also takes the Adam step
+        and writes the next pack's scales when the call qualifies; `self.tail_fused` says whether it did
+        (False: the caller runs Adam)."""
         lib = _lib.load()
         r = self.r
         dev = rays_o.device
@@ -397,10 +400,22 @@ class MapPass:
         bws = torch.empty(lib.pnr_map_bwd_workspace_bytes(ctypes_ref(prm), n), dtype=torch.uint8, device=dev)
         loss = torch.empty((), dtype=torch.float64, device=dev)
         arr = _lib.PtrArray(*[g.data_ptr() for g in grads])
-        _lib.check(lib.pnr_map_step(ctypes_ref(prm), _lib.ptr(packed), _lib.ptr(rays_o), _lib.ptr(rays_d),
-                                    _lib.ptr(gt_depth), _lib.ptr(gt_color), _lib.ptr(t_rand), n, float(w_color),
-                                    float(w_reg), _lib.ptr(loss), arr, _lib.ptr(ws), ws.numel(), _lib.ptr(bws),
-                                    bws.numel(), _lib.ptr(loss_ws), _lib.stream_of(dev)), 'map_step')
+        self.tail_fused = False
+        if tail is not None:
+            import ctypes
+            fused = ctypes.c_int32(0)
+            _lib.check(lib.pnr_map_step_adam(ctypes_ref(prm), _lib.ptr(packed), _lib.ptr(rays_o), _lib.ptr(rays_d),
+                                             _lib.ptr(gt_depth), _lib.ptr(gt_color), _lib.ptr(t_rand), n,
+                                             float(w_color), float(w_reg), _lib.ptr(loss), arr, _lib.ptr(ws),
+                                             ws.numel(), _lib.ptr(bws), bws.numel(), _lib.ptr(loss_ws),
+                                             ctypes.byref(tail), ctypes.byref(fused), _lib.stream_of(dev)),
+                       'map_step_adam')
+            self.tail_fused = bool(fused.value)
+        else:
+            _lib.check(lib.pnr_map_step(ctypes_ref(prm), _lib.ptr(packed), _lib.ptr(rays_o), _lib.ptr(rays_d),
+                                        _lib.ptr(gt_depth), _lib.ptr(gt_color), _lib.ptr(t_rand), n, float(w_color),
+                                        float(w_reg), _lib.ptr(loss), arr, _lib.ptr(ws), ws.numel(), _lib.ptr(bws),
+                                        bws.numel(), _lib.ptr(loss_ws), _lib.stream_of(dev)), 'map_step')
         prm.points = None
         return loss
 
