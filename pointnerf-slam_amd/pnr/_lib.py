@@ -31,7 +31,7 @@ STATUS_F16_RANGE = 1  # include/pnr.h PNR_STATUS_F16_RANGE
 
 
 def precision_code(name) -> int:
-    """PNR_PREC_* code of a precision name ('fp32' | 'bf16x3' | 'bf16')."""
+    """PNR_PREC_* code of a precision name ('fp32' | 'bf16x3' | 'bf16' | 'f16x3')."""
     if name not in PRECISIONS:
         raise ValueError(f'pnr: unknown decoder precision {name!r} (one of {sorted(PRECISIONS)})')
     return PRECISIONS[name]

@@ -36,6 +36,7 @@ import torch
 from conftest import golden_params, load_golden
 from oracle import ref_points as RP
 from oracle import ref_render as RR
+from split_model import decode_save
 from test_gpu_points import grad_elementwise, mag_arrays, surface_cloud
 
 pytestmark = pytest.mark.gpu
@@ -127,13 +128,11 @@ def edge_free(params, q, xyz, pdict, return_z=False):
 def hip_relu_decisions(pnr_mod, dec, x, c, prec):
     """The ReLU decisions [z > 0] of the HIP training forward (pnr_mlp_fwd_train_c) for points x (P,3)
     float32 and features c (P,32): its saved mask words (capi.cpp carve_save: e [ld][96], h [4][ld][256]
-    fp32, x [ld] float4, then the masks [4][ld/32][64 lanes] uint4; unit u of lane half (u >> 2) & 1,
-    word u >> 6, bit 16 ((u >> 5) & 1) + 4 ((u >> 3) & 3) + (u & 3): k_mlp_fwd16 conv1 / mlp.hip
-    save_mask), decoded to a bool (4, P, 256)."""
+    fp32, x [ld] float4, then the masks [4][ld/32][64 lanes] uint4), decoded to a bool (4, P, 256) by
+    split_model.decode_save, which states the bit mapping."""
     from pnr import _lib
     lib = pnr_mod.library()
     P = x.shape[0]
-    ld = -(-P // 128) * 128
     dev = x.device
     ws = torch.empty(lib.pnr_mlp_train_workspace_bytes(P), dtype=torch.uint8, device=dev)
     raw = torch.empty((P, 4), device=dev)
@@ -143,13 +142,7 @@ def hip_relu_decisions(pnr_mod, dec, x, c, prec):
                                        _lib.ptr(ws), ws.numel(), _lib.precision_code(prec), _lib.stream_of(dev)),
                'mlp_fwd_train_c')
     torch.cuda.synchronize()
-    off = (96 + 4 * 256) * 4 * ld + 16 * ld
-    words = ws[off:off + 128 * ld].view(torch.int32).view(4, ld // 32, 2, 32, 4).cpu().long() & 0xFFFFFFFF
-    u = torch.arange(256)
-    hh, wi, bit = (u >> 2) & 1, u >> 6, 16 * ((u >> 5) & 1) + 4 * ((u >> 3) & 3) + (u & 3)
-    p = torch.arange(P)
-    w = words[:, (p >> 5)[:, None], hh[None, :], (p & 31)[:, None], wi[None, :]]  # (4, P, 256)
-    return ((w >> bit[None, None, :]) & 1).bool()
+    return decode_save(ws, P)['masks'][:, :P].cpu()
 
 
 @pytest.mark.parametrize('mode', ['idw', 'trilinear'])
