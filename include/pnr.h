@@ -198,7 +198,8 @@ int pnr_mlp_bwd(const float* packed, int64_t P, const float* g_raw, float* const
  * float64 render).  Outputs: depth, var (n) float64, rgb (n,3), sigma (n, N_samples) float32 -- bit for
  * bit those of pnr_render_fwd + pnr_regulation_fwd with the same t_rand (tests/test_gpu_mapping.py).
  * pnr_map_bwd takes dL/ddepth, dL/drgb, dL/dsigma and runs ONE delta chain / weight-gradient pass over
- * every sample (grads accumulated, +=; neural points as in pnr_render_bwd); no ray gradients.
+ * every sample (grads accumulated, +=; neural points as in pnr_render_bwd); no ray gradients
+ * (pnr_map_bwd_rays is the form with them).
  * prm: save_for_backward / need_ray_grads ignored (the pass always trains the decoder); n_importance > 0;
  * far_mode as pnr_render_fwd; t_rand (n, N_samples) float32 in [0,1). */
 size_t pnr_map_workspace_bytes(const pnr_render_params* prm, int64_t n_rays);
@@ -423,6 +424,54 @@ int pnr_window_sample_pack(uint64_t seed, void* state, int64_t n, int64_t n_per_
                            int32_t n_samples, float* rays_o, float* rays_d, float* gt_depth, float* gt_color,
                            float* t_rand, int64_t* idx, float* far_clamp, const float* const* params, float* packed,
                            const float* scales, void* stream);
+
+/* ---- bundle adjustment (src/Mapper.py:460-500, 542-543, 567-581, 675-692; additions to ABI 14) ----
+ * With mapping.BA the Mapper's loss also reaches the camera tensors of the window's keyframes, through
+ * rays_o, rays_d and |rays_d|.  The map pass in its ray-gradient form: the delta chain also emits dL/dx
+ * per sample, the gather backward (neural points) adds its dL/dp into the same buffer, and ONE more
+ * launch (k_map_ray_grads) sums per ray, over its regulation, coarse and importance rows,
+ *   dL/drays_o = sum g_x,   dL/drays_d = sum g_x z + g_nrm d / |d|       (float64 sums, a fixed order)
+ * with the regulation's float32 z (Renderer.py:284-294, recomputed from gt_depth, t_vals and t_rand),
+ * the render's saved float64 z, and no gradient through the importance z (detached, Renderer.py:190)
+ * or near / far.  g_rays_o, g_rays_d: (n,3) float32, written.  Everything else -- the decoder / fc_c /
+ * feature gradients, the loss, the fused tail -- is bit for bit that of the form without ray gradients.
+ * pnr_map_bwd_rays = pnr_map_bwd (+ gt_depth, t_rand of the forward); pnr_map_step_rays = pnr_map_step
+ * (tail NULL; fused may be NULL) or pnr_map_step_adam (tail given).  n = 0: as those calls, the ray
+ * gradients (no rows) untouched. */
+int pnr_map_bwd_rays(const pnr_render_params* prm, const float* packed, const float* rays_d, const float* gt_depth,
+                     const float* t_rand, int64_t n, const double* g_depth, const float* g_rgb, const float* g_sigma,
+                     float* const* grads, float* g_rays_o, float* g_rays_d, void* workspace, size_t ws_bytes,
+                     void* bwd_ws, size_t bwd_bytes, void* stream);
+int pnr_map_step_rays(const pnr_render_params* prm, const float* packed, const float* rays_o, const float* rays_d,
+                      const float* gt_depth, const float* gt_color, const float* t_rand, int64_t n, float w_color,
+                      float w_reg, double* loss, float* const* grads, void* workspace, size_t ws_bytes, void* bwd_ws,
+                      size_t bwd_bytes, void* loss_ws, const pnr_adam_tail* tail, int32_t* fused, float* g_rays_o,
+                      float* g_rays_d, void* stream);
+
+/* The pose gradient, the camera Adam step and the pose table in ONE launch.  The n = n_frames *
+ * n_per_frame rays are those of pnr_window_rays: frame f's rays at [f n_per_frame, (f+1) n_per_frame),
+ * pixel idx[r] (int64, row-major in the H x W image, clamped as there).  Per frame
+ *   dL/dt = sum g_rays_o,   dL/dR[i][j] = sum g_rays_d[i] dir[j],   dir = ((i-cx)/fx, -(j-cy)/fy, -1)
+ * (the adjoint of get_rays_from_uv, src/common.py:74-89; dir in float32 as the forward forms it, the
+ * sums in float64), chained through quad2rotation (src/common.py:137-160: R = I + two_s A(q) with
+ * two_s = 2 / sum q^2, so a non-unit quaternion's normalisation term is part of the gradient) into
+ *   g_cam (F,7) float32: dL/d(qw, qx, qy, qz, tx, ty, tz), written; a fixed frame's row is zero.
+ * adam = 1: every frame with fixed[f] == 0 then takes torch.optim.Adam's step (lr, beta1, beta2, eps;
+ * moments m, v (F,7); step number *step + 1, *step a device int32 of completed steps that this launch
+ * advances by one) on its row of cam (F,7), and its c2w (F,4,4) row is rewritten from the stepped
+ * tensor (get_camera_from_tensor, bottom row 0 0 0 1).  A fixed frame's cam, m, v and c2w rows are
+ * not written at all.  adam = 0: gradients only (cam is read; m, v, step, c2w may be NULL).
+ * fixed: (F) bytes, or NULL = no frame fixed.  workspace: pnr_pose_step_workspace_bytes(n_frames,
+ * n_per_frame) bytes, 8-byte aligned, ZERO-FILLED before its first use (a ticket word; each call leaves
+ * it zero) and not shared by concurrent calls.  Deterministic: float64 block partials in a fixed order,
+ * added by the block that takes the last ticket in block order; no floating-point atomics.
+ * n_frames = 0 or n_per_frame = 0: a no-op that leaves the poses (and g_cam) untouched. */
+size_t pnr_pose_step_workspace_bytes(int64_t n_frames, int64_t n_per_frame);
+int pnr_pose_step(const float* g_rays_o, const float* g_rays_d, const int64_t* idx, int64_t n_frames,
+                  int64_t n_per_frame, int32_t H, int32_t W, float fx, float fy, float cx, float cy, float* cam,
+                  const uint8_t* fixed, float* m, float* v, float lr, float beta1, float beta2, float eps,
+                  int32_t* step, int32_t adam, float* c2w, float* g_cam, void* workspace, size_t ws_bytes,
+                  void* stream);
 
 /* ---- mesh extraction (src/utils/Mesher.py:349-574; additions to ABI 14) -------------------------
  * Mesher.point_masks (:53-212) for one chunk of P float32 points (the caller splits by

@@ -70,6 +70,13 @@ int launch_fine_loss(const pnr_render_params&, const float*, const double*, cons
                      const float4*, const float4*, int64_t, const float*, const float*, float, float, const float*,
                      const float4*, float*, float*, float*, float*, float*, int, float*, int, float*, int, double*,
                      uint32_t*, double*, hipStream_t);
+int launch_map_ray_grads(const pnr_render_params&, const float*, const float*, const float*, const double*,
+                         const double*, const float*, int64_t, int64_t, const float*, int64_t, float*, float*,
+                         hipStream_t);
+int64_t pose_step_workspace_bytes(int64_t F, int64_t npf);
+int launch_pose_step(const float*, const float*, const int64_t*, int, int64_t, int, int, float, float, float, float,
+                     float*, const uint8_t*, float*, float*, float, float, float, float, int32_t*, int, float*, float*,
+                     void*, hipStream_t);
 int64_t point_masks_parts(int64_t P);
 int launch_point_masks(const float*, int64_t, const float*, int, int, int, float, float, float, float, int,
                        const float*, const float*, uint8_t*, uint8_t*, float*, hipStream_t);
@@ -293,15 +300,30 @@ __global__ void k_fill(float* p, int64_t n, float v) {
 
 // Store semantics (grads_overwrite) with nothing to store: the weight gradients of an empty batch
 // are zero, exactly as autograd's would be (an early return would leave the previous step's values).
+// One launch zeroes every tensor.  (Not hipMemsetAsync per tensor: captured into a graph whose batch
+// the window sampler draws, the memset node of the 1,116-byte dL/dB came back from the second replay on
+// with one wrong word in every 8 or 16 of its first 1,104 bytes -- fp32 precision, with or without
+// bundle adjustment; eager calls and static-batch graphs were right.  tests/test_gpu_ba.py replays it.)
+struct ZeroJobs {
+  float* p[PNR_N_PARAMS + PNR_N_FC_PARAMS];
+  int64_t n[PNR_N_PARAMS + PNR_N_FC_PARAMS];
+};
+__global__ void k_zero_multi(ZeroJobs z) {
+  float* p = z.p[blockIdx.y];
+  const int64_t n = z.n[blockIdx.y];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    p[i] = 0.f;
+}
 int zero_weight_grads(float* const* grads, float* const* g_fc, hipStream_t st) {
   static const int64_t dec_n[PNR_N_PARAMS] = {3 * kFourier, kHidden * kFourier, kHidden, kHidden * kHidden, kHidden,
                                               kHidden * kHidden, kHidden, kHidden * kHidden, kHidden, 4 * kHidden, 4};
-  for (int i = 0; grads && i < PNR_N_PARAMS; ++i)
-    if (int rc = hip_status(hipMemsetAsync(grads[i], 0, dec_n[i] * sizeof(float), st))) return rc;
-  for (int i = 0; g_fc && i < PNR_N_FC_PARAMS; ++i)
-    if (int rc = hip_status(hipMemsetAsync(g_fc[i], 0, (i % 2 ? kHidden : kHidden * kCDim) * sizeof(float), st)))
-      return rc;
-  return PNR_OK;
+  ZeroJobs z{};
+  int k = 0;
+  for (int i = 0; grads && i < PNR_N_PARAMS; ++i, ++k) z.p[k] = grads[i], z.n[k] = dec_n[i];
+  for (int i = 0; g_fc && i < PNR_N_FC_PARAMS; ++i, ++k) z.p[k] = g_fc[i], z.n[k] = i % 2 ? kHidden : kHidden * kCDim;
+  if (k == 0) return PNR_OK;
+  hipLaunchKernelGGL(k_zero_multi, dim3(64, (unsigned)k), dim3(256), 0, st, z);
+  return hip_status(hipGetLastError());
 }
 
 // Shared backward core over P points with saved activations `sv` and dL/draw in b.g_out.
@@ -985,10 +1007,18 @@ int map_fwd_core(const pnr_render_params* prm, const float* packed, const float*
 }
 
 // The map pass's backward on carved workspaces: the compositing backward into b.g_out (unless the
-// fused tail already wrote it: `fine_done`), the delta chain / weight gradients and the gather backward
+// fused tail already wrote it: `fine_done`), the delta chain / weight gradients and the gather backward.
+// `rg` (bundle adjustment): the delta chain also emits dL/dx, the gather backward adds its dL/dp, and
+// k_map_ray_grads sums them per ray into rg->g_o / rg->g_d -- one launch more; nothing else changes
+struct MapRayGrads {
+  const float* gt_depth;
+  const float* t_rand;
+  float* g_o;
+  float* g_d;
+};
 int map_bwd_core(const pnr_render_params* prm, const float* packed, const float* rays_d, int64_t n, const MapWS& w,
                  BwdWS& b, const double* g_depth, const float* g_rgb, const float* g_sigma, float* const* grads,
-                 bool fine_done, hipStream_t st, const AdamTail* tail = nullptr) {
+                 bool fine_done, hipStream_t st, const AdamTail* tail = nullptr, const MapRayGrads* rg = nullptr) {
   const int S = prm->n_samples, I = prm->n_importance;
   const double* zi = w.z + n * S;
   const float4* x4 = w.save.xP;
@@ -1005,13 +1035,15 @@ int map_bwd_core(const pnr_render_params* prm, const float* packed, const float*
     if (rc) return rc;
   }
   FeatBwd fb{pts ? pts->fc_packed : nullptr, w.c, pts ? pts->g_fc : nullptr};
-  rc = mlp_backward_core(prm->precision, packed, w.save, w.ld, b, grads, false, st, pts ? &fb : nullptr,
+  rc = mlp_backward_core(prm->precision, packed, w.save, w.ld, b, grads, rg != nullptr, st, pts ? &fb : nullptr,
                          prm->grads_overwrite != 0, tail);
   if (rc) return rc;
   if (pts)
-    rc = launch_gather_bwd(*pts, nullptr, kPtsX4, x4, w.ld, w.nidx, w.nw, w.c, b.g_c, nullptr, true, b.gws, b.gws_bytes,
-                           st);
-  return rc;
+    rc = launch_gather_bwd(*pts, nullptr, kPtsX4, x4, w.ld, w.nidx, w.nw, w.c, b.g_c, rg ? b.g_x : nullptr, true,
+                           b.gws, b.gws_bytes, st);
+  if (rc || !rg) return rc;
+  return launch_map_ray_grads(*prm, rays_d, rg->gt_depth, rg->t_rand, w.z, zi, b.g_x, w.pr, w.r1, b.g_nrm, n, rg->g_o,
+                              rg->g_d, st);
 }
 
 // pnr_map_step's per-ray scratch after the map workspace: the unfused tail's depth / var / rgb /
@@ -1057,10 +1089,12 @@ size_t pnr_map_bwd_workspace_bytes(const pnr_render_params* prm, int64_t n_rays)
   return b;
 }
 
-int pnr_map_bwd(const pnr_render_params* prm, const float* packed, const float* rays_d, int64_t n,
-                const double* g_depth, const float* g_rgb, const float* g_sigma, float* const* grads, void* workspace,
-                size_t ws_bytes, void* bwd_ws, size_t bwd_bytes, void* stream) {
+static int map_bwd_impl(const pnr_render_params* prm, const float* packed, const float* rays_d, int64_t n,
+                        const double* g_depth, const float* g_rgb, const float* g_sigma, float* const* grads,
+                        void* workspace, size_t ws_bytes, void* bwd_ws, size_t bwd_bytes, const MapRayGrads* rg,
+                        void* stream) {
   if (!valid_map_prm(prm) || !packed || n < 0) return PNR_E_ARG;
+  if (rg && (!rg->g_o || !rg->g_d || (n > 0 && (!rg->gt_depth || !rg->t_rand)))) return PNR_E_ARG;
   if (n == 0) {  // store semantics: an empty batch's weight gradients are zero
     if (!prm->grads_overwrite) return PNR_OK;
     if (grads)
@@ -1077,7 +1111,24 @@ int pnr_map_bwd(const pnr_render_params* prm, const float* packed, const float* 
   const pnr_points* pts = prm->points;
   BwdWS b = carve_bwd(w.ld, n, bwd_ws, &bneed, pts != nullptr, true, n_pts(prm));
   if (ws_bytes < need || bwd_bytes < bneed) return PNR_E_WORKSPACE;
-  return map_bwd_core(prm, packed, rays_d, n, w, b, g_depth, g_rgb, g_sigma, grads, false, (hipStream_t)stream);
+  return map_bwd_core(prm, packed, rays_d, n, w, b, g_depth, g_rgb, g_sigma, grads, false, (hipStream_t)stream,
+                      nullptr, rg);
+}
+
+int pnr_map_bwd(const pnr_render_params* prm, const float* packed, const float* rays_d, int64_t n,
+                const double* g_depth, const float* g_rgb, const float* g_sigma, float* const* grads, void* workspace,
+                size_t ws_bytes, void* bwd_ws, size_t bwd_bytes, void* stream) {
+  return map_bwd_impl(prm, packed, rays_d, n, g_depth, g_rgb, g_sigma, grads, workspace, ws_bytes, bwd_ws, bwd_bytes,
+                      nullptr, stream);
+}
+
+int pnr_map_bwd_rays(const pnr_render_params* prm, const float* packed, const float* rays_d, const float* gt_depth,
+                     const float* t_rand, int64_t n, const double* g_depth, const float* g_rgb, const float* g_sigma,
+                     float* const* grads, float* g_rays_o, float* g_rays_d, void* workspace, size_t ws_bytes,
+                     void* bwd_ws, size_t bwd_bytes, void* stream) {
+  const MapRayGrads rg{gt_depth, t_rand, g_rays_o, g_rays_d};
+  return map_bwd_impl(prm, packed, rays_d, n, g_depth, g_rgb, g_sigma, grads, workspace, ws_bytes, bwd_ws, bwd_bytes,
+                      &rg, stream);
 }
 
 size_t pnr_map_step_workspace_bytes(const pnr_render_params* prm, int64_t n_rays) {
@@ -1094,8 +1145,9 @@ static int map_step_impl(const pnr_render_params* prm, const float* packed, cons
                          const float* gt_depth, const float* gt_color, const float* t_rand, int64_t n, float w_color,
                          float w_reg, double* loss, float* const* grads, void* workspace, size_t ws_bytes,
                          void* bwd_ws, size_t bwd_bytes, void* loss_ws, const pnr_adam_tail* tail, int32_t* fused,
-                         void* stream) {
+                         void* stream, float* g_rays_o = nullptr, float* g_rays_d = nullptr, bool rays = false) {
   if (!valid_map_prm(prm) || !packed || n < 0 || !loss || !loss_ws) return PNR_E_ARG;
+  if (rays && (!g_rays_o || !g_rays_d)) return PNR_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   if (fused) *fused = 0;
   if (grads)
@@ -1141,8 +1193,9 @@ static int map_step_impl(const pnr_render_params* prm, const float* packed, cons
                          sw.g_depth, sw.g_rgb, sw.g_sigma, st);
   }
   if (rc) return rc;
+  const MapRayGrads rg{gt_depth, t_rand, g_rays_o, g_rays_d};
   rc = map_bwd_core(prm, packed, rays_d, n, w, b, sw.g_depth, sw.g_rgb, sw.g_sigma, grads, fuse, st,
-                    tail_ok ? &at : nullptr);
+                    tail_ok ? &at : nullptr, rays ? &rg : nullptr);
   if (rc == 0 && tail_ok && fused) *fused = 1;
   return rc;
 }
@@ -1157,10 +1210,8 @@ int pnr_map_step(const pnr_render_params* prm, const float* packed, const float*
 
 size_t pnr_step_tail_floats(void) { return (size_t)kStepTailFloats; }
 
-int pnr_map_step_adam(const pnr_render_params* prm, const float* packed, const float* rays_o, const float* rays_d,
-                      const float* gt_depth, const float* gt_color, const float* t_rand, int64_t n, float w_color,
-                      float w_reg, double* loss, float* const* grads, void* workspace, size_t ws_bytes, void* bwd_ws,
-                      size_t bwd_bytes, void* loss_ws, const pnr_adam_tail* tail, int32_t* fused, void* stream) {
+// pnr_map_step_adam's conditions on its tail descriptor
+static int check_adam_tail(const pnr_adam_tail* tail, const int32_t* fused, float* const* grads) {
   static const int64_t dec_n[PNR_N_PARAMS] = {3 * kFourier, kHidden * kFourier, kHidden, kHidden * kHidden, kHidden,
                                               kHidden * kHidden, kHidden, kHidden * kHidden, kHidden, 4 * kHidden, 4};
   if (!tail || !fused || tail->n < 0 || !tail->step2 || !tail->scales ||
@@ -1183,8 +1234,48 @@ int pnr_map_step_adam(const pnr_render_params* prm, const float* packed, const f
     }
     if (at != tail->n) return PNR_E_ARG;
   }
+  return PNR_OK;
+}
+
+int pnr_map_step_adam(const pnr_render_params* prm, const float* packed, const float* rays_o, const float* rays_d,
+                      const float* gt_depth, const float* gt_color, const float* t_rand, int64_t n, float w_color,
+                      float w_reg, double* loss, float* const* grads, void* workspace, size_t ws_bytes, void* bwd_ws,
+                      size_t bwd_bytes, void* loss_ws, const pnr_adam_tail* tail, int32_t* fused, void* stream) {
+  if (int rc = check_adam_tail(tail, fused, grads)) return rc;
   return map_step_impl(prm, packed, rays_o, rays_d, gt_depth, gt_color, t_rand, n, w_color, w_reg, loss, grads,
                        workspace, ws_bytes, bwd_ws, bwd_bytes, loss_ws, tail, fused, stream);
+}
+
+int pnr_map_step_rays(const pnr_render_params* prm, const float* packed, const float* rays_o, const float* rays_d,
+                      const float* gt_depth, const float* gt_color, const float* t_rand, int64_t n, float w_color,
+                      float w_reg, double* loss, float* const* grads, void* workspace, size_t ws_bytes, void* bwd_ws,
+                      size_t bwd_bytes, void* loss_ws, const pnr_adam_tail* tail, int32_t* fused, float* g_rays_o,
+                      float* g_rays_d, void* stream) {
+  if (tail)
+    if (int rc = check_adam_tail(tail, fused, grads)) return rc;
+  return map_step_impl(prm, packed, rays_o, rays_d, gt_depth, gt_color, t_rand, n, w_color, w_reg, loss, grads,
+                       workspace, ws_bytes, bwd_ws, bwd_bytes, loss_ws, tail, fused, stream, g_rays_o, g_rays_d, true);
+}
+
+size_t pnr_pose_step_workspace_bytes(int64_t n_frames, int64_t n_per_frame) {
+  if (n_frames < 0 || n_per_frame < 0 || n_frames > (1 << 16)) return 0;
+  return (size_t)pose_step_workspace_bytes(n_frames, n_per_frame);
+}
+
+int pnr_pose_step(const float* g_rays_o, const float* g_rays_d, const int64_t* idx, int64_t n_frames,
+                  int64_t n_per_frame, int32_t H, int32_t W, float fx, float fy, float cx, float cy, float* cam,
+                  const uint8_t* fixed, float* m, float* v, float lr, float beta1, float beta2, float eps,
+                  int32_t* step, int32_t adam, float* c2w, float* g_cam, void* workspace, size_t ws_bytes,
+                  void* stream) {
+  if (n_frames < 0 || n_per_frame < 0 || n_frames > (1 << 16) || (adam != 0 && adam != 1)) return PNR_E_ARG;
+  if (n_frames == 0 || n_per_frame == 0) return PNR_OK;  // no rays: the poses stay as they are
+  if (!g_rays_o || !g_rays_d || !idx || !cam || !g_cam || !workspace || H < 1 || W < 1 || fx == 0.f || fy == 0.f)
+    return PNR_E_ARG;
+  if (adam && (!m || !v || !step || !c2w)) return PNR_E_ARG;
+  if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0) return PNR_E_ARG;
+  if (ws_bytes < (size_t)pose_step_workspace_bytes(n_frames, n_per_frame)) return PNR_E_WORKSPACE;
+  return launch_pose_step(g_rays_o, g_rays_d, idx, (int)n_frames, n_per_frame, H, W, fx, fy, cx, cy, cam, fixed, m, v,
+                          lr, beta1, beta2, eps, step, adam, c2w, g_cam, workspace, (hipStream_t)stream);
 }
 
 int pnr_mlp_pack_scaled(const float* const* params, float* packed, const float* scales, void* stream) {

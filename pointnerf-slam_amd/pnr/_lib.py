@@ -123,6 +123,18 @@ _SIGS = {
                                          c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                          c_size_t, c_void_p, c_size_t, c_void_p, ctypes.POINTER(AdamTail),
                                          ctypes.POINTER(c_int32), c_void_p]),
+    'pnr_map_bwd_rays': (ctypes.c_int, [ctypes.POINTER(RenderParams), c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_size_t, c_void_p, c_size_t, c_void_p]),
+    'pnr_map_step_rays': (ctypes.c_int, [ctypes.POINTER(RenderParams), c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                         c_size_t, c_void_p, c_size_t, c_void_p, ctypes.POINTER(AdamTail),
+                                         ctypes.POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
+    'pnr_pose_step_workspace_bytes': (c_size_t, [c_int64, c_int64]),
+    'pnr_pose_step': (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_float,
+                                     c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                     c_float, c_float, c_float, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                     c_size_t, c_void_p]),
     'pnr_mlp_pack_scaled': (ctypes.c_int, [PtrArray, c_void_p, c_void_p, c_void_p]),
     'pnr_window_sample_pack': (ctypes.c_int, [ctypes.c_uint64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_float,
                                               c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int32,

@@ -19,6 +19,12 @@ summation order (no GPU sum is); tests/test_gpu_precision.py holds it to the cor
 gradient.  The point-feature gradient (neural points) is summed exactly in int64 fixed point
 (include/pnr.h, ABI 10), so it does not depend on scheduling either: a neural-point step reruns and
 replays bit for bit too.
+
+Bundle adjustment (mapping.BA, src/Mapper.py:460-500, 567-581, 675-692): `MapStep(..., ba=BundleAdjust(
+sampler, cam_lr))` adds the camera tensors of the window's keyframes as a second parameter group.  The
+map pass then also emits the ray gradients (one launch more), and ONE pnr_pose_step launch forms the
+(F,7) camera-tensor gradient, takes the camera Adam step and rewrites the sampler's c2w table, so the
+next iteration's rays come from the stepped poses.  Deterministic like the rest of the step.
 """
 from __future__ import annotations
 
@@ -118,6 +124,77 @@ class Adam:
             self.on_update()
 
 
+class BundleAdjust:
+    """The camera-tensor parameter group of Mapper.optimize_map under mapping.BA (src/Mapper.py:460-500):
+    one (qw, qx, qy, qz, tx, ty, tz) tensor per frame of a WindowSampler's window (get_tensor_from_camera
+    of its poses), Adam moments for them, and the step itself (pnr_pose_step: pose gradient from the ray
+    gradients, Adam with lr = mapping.BA_cam_lr on the frames that are not fixed, and their rows of the
+    pose table rewritten from the stepped tensors -- one launch).
+
+    `self.c2w` IS `sampler.c2w` (the same storage): the sampler's next batch is drawn from the stepped
+    poses.  As in the reference, whose rays come from get_camera_from_tensor(camera_tensor) from the
+    first iteration on (:567-581), the rows of the frames that are not fixed are rewritten from their
+    tensors here.  `fixed`: frame indices that stay put, default the oldest frame (:464-465).
+    `poses()` is the (F,4,4) est_c2w of the write-back (:675-690), `camera_tensors()` the (F,7) tensors;
+    `g_cam` holds the last step's camera gradient (zero rows for the fixed frames)."""
+
+    def __init__(self, sampler, cam_lr, fixed=(0,), betas=(0.9, 0.999), eps=1e-8):
+        from .common import get_tensor_from_camera
+        self.sampler = sampler
+        self.c2w = sampler.c2w
+        dev = self.c2w.device
+        F = self.c2w.shape[0]
+        self.fixed = tuple(sorted({int(f) % F for f in fixed}))
+        self.fixed_mask = torch.zeros(F, dtype=torch.uint8)
+        for f in self.fixed:
+            self.fixed_mask[f] = 1
+        self.fixed_mask = self.fixed_mask.to(dev)
+        self.lr = float(cam_lr)
+        self.b1, self.b2 = betas
+        self.eps = eps
+        self.cam = torch.empty((F, 7), dtype=torch.float32, device=dev)
+        self.m = torch.zeros((F, 7), dtype=torch.float32, device=dev)
+        self.v = torch.zeros((F, 7), dtype=torch.float32, device=dev)
+        self.g_cam = torch.zeros((F, 7), dtype=torch.float32, device=dev)
+        self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)  # completed camera Adam steps
+        self.ws = torch.zeros(_lib.load().pnr_pose_step_workspace_bytes(F, int(sampler.n)), dtype=torch.uint8,
+                              device=dev)
+        self.set_camera_tensors(torch.stack([get_tensor_from_camera(self.c2w[f].cpu()) for f in range(F)]))
+
+    def set_camera_tensors(self, cam):
+        """Take (F,7) camera tensors (any quaternion norm) and rewrite the pose-table rows of the frames
+        that are not fixed from them (get_camera_from_tensor)."""
+        from .common import get_camera_from_tensor
+        self.cam.copy_(cam.detach().to(self.cam.device, torch.float32))
+        free = [f for f in range(self.cam.shape[0]) if f not in self.fixed]
+        if free:
+            self.c2w[free, :3, :] = get_camera_from_tensor(self.cam[free])
+
+    def camera_tensors(self):
+        return self.cam.detach().clone()
+
+    def poses(self):
+        return self.c2w.detach().clone()
+
+    def step(self, g_rays_o, g_rays_d, idx=None, adam=True):
+        """pnr_pose_step on the ray gradients of the batch drawn from `idx` (default: the sampler's last
+        batch).  adam=False: `g_cam` only."""
+        idx = self.sampler.idx if idx is None else idx
+        F, H, W = self.sampler.depth.shape
+        npf = int(self.sampler.n)
+        if idx is None or idx.numel() != F * npf or g_rays_o.shape[0] != F * npf or g_rays_d.shape[0] != F * npf:
+            raise ValueError('pnr.BundleAdjust: the ray gradients do not belong to the window sampler\'s last batch '
+                             f'({F} frames x {npf} pixels)')
+        dev = self.cam.device
+        _lib.require_cuda(g_rays_o, g_rays_d, idx, self.cam, self.c2w)
+        fx, fy, cx, cy = [float(x) for x in self.sampler.cam]
+        _lib.check(_lib.load().pnr_pose_step(
+            _lib.ptr(g_rays_o), _lib.ptr(g_rays_d), _lib.ptr(idx), F, npf, H, W, fx, fy, cx, cy, _lib.ptr(self.cam),
+            _lib.ptr(self.fixed_mask), _lib.ptr(self.m), _lib.ptr(self.v), self.lr, self.b1, self.b2, self.eps,
+            _lib.ptr(self.step_dev), 1 if adam else 0, _lib.ptr(self.c2w), _lib.ptr(self.g_cam), _lib.ptr(self.ws),
+            self.ws.numel(), _lib.stream_of(dev)), 'pose_step')
+
+
 class MapStep:
     """One Mapper iteration.  Default (`fused=True`): the render and the regulation are ONE decoder
     pass (pnr.renderer.MapPass -> pnr_map_fwd / pnr_map_bwd): the regulation and coarse samples share
@@ -128,7 +205,11 @@ class MapStep:
     `fused=False` keeps the two-chain form: the regulation's forward, loss term and backward on a side
     stream with its own gradient buffer (`overlap` True / 'auto' up to OVERLAP_MAX_RAYS rays) or on the
     caller's stream (`overlap=False`), joined before the gradients are summed (render + regulation, a
-    fixed order).  No path goes through autograd (MapStep.loss is the autograd drop-in form)."""
+    fixed order).  No path goes through autograd (MapStep.loss is the autograd drop-in form).
+    `ba` (a BundleAdjust over the WindowSampler that draws the batches): every path also produces the
+    ray gradients and ends with the pose step on the pixel indices of the batch just drawn -- two
+    launches more on the fused paths (k_map_ray_grads, k_pose_step); the two-chain form pays one ray
+    kernel per chain and their sum as well.  The fused reduce + Adam + scales tail stays eligible."""
 
     OVERLAP_MAX_RAYS = 32768
     # the fused path as one pnr_map_step call (ABI 13) rather than pnr_map_fwd + pnr_map_loss + pnr_map_bwd
@@ -138,7 +219,11 @@ class MapStep:
     fuse_tail = True
 
     def __init__(self, renderer, decoder, lr=2e-4, w_color_loss=0.05, w_reg=0.0005, ddp=None, points=None,
-                 feat_lr=None, overlap='auto', fused=True):
+                 feat_lr=None, overlap='auto', fused=True, ba=None):
+        if ba is not None and ddp is not None:
+            raise NotImplementedError('pnr.MapStep: bundle adjustment under data parallel is not built (the camera '
+                                      'gradient would need its own all-reduce)')
+        self.ba = ba
         self.renderer = renderer
         self.decoder = decoder
         self.points = points
@@ -241,17 +326,30 @@ class MapStep:
             else:
                 self.points.invalidate_feats()  # the f16 feature copy, if any
 
-    def _regulation_chain(self, views, rays_o, rays_d, gt_depth, t_rand):
+    def _regulation_chain(self, views, rays_o, rays_d, gt_depth, t_rand, ray_grads=None):
         from .renderer import TrainPass, map_loss
         reg = TrainPass(self.renderer, self.c, self.decoder, 'regulation')
         (sigma,) = reg.forward(rays_o, rays_d, gt_depth, t_rand=t_rand)
         loss, _, _, g_s = map_loss(None, None, None, None, 0.0, sigma=sigma, w_reg=self.w_reg, ws=self._loss_ws('side'))
-        reg.backward(views[0], g_fc=views[1], g_feats=views[2], g_sigma=g_s)
+        reg.backward(views[0], g_fc=views[1], g_feats=views[2], g_sigma=g_s, ray_grads=ray_grads)
         return loss
 
     def __call__(self, rays_o, rays_d, gt_depth, gt_color, t_rand=None, far_clamp=None):
         """One Mapper iteration.  far_clamp (optional): the batch's max(1.2 gt) as a device scalar
         (e.g. from WindowSampler), else computed by the render pass (or all-reduced, data parallel)."""
+        if self.ba is None:
+            return self._iterate(rays_o, rays_d, gt_depth, gt_color, t_rand, far_clamp, None)
+        # bundle adjustment: the pass also writes dL/drays_o, dL/drays_d; the pose step ends the iteration
+        idx = self.ba.sampler.idx
+        if idx is None or idx.numel() != rays_o.shape[0]:
+            raise ValueError('pnr.MapStep: with `ba` the batch must be the window sampler\'s last batch (its pixel '
+                             'indices give the pose gradient)')
+        rg = torch.empty((2, rays_o.shape[0], 3), dtype=torch.float32, device=rays_o.device)
+        loss = self._iterate(rays_o, rays_d, gt_depth, gt_color, t_rand, far_clamp, rg)
+        self.ba.step(rg[0], rg[1])
+        return loss
+
+    def _iterate(self, rays_o, rays_d, gt_depth, gt_color, t_rand, far_clamp, rg):
         from .renderer import TrainPass, map_loss
         r = self.renderer
         dev = rays_o.device
@@ -286,7 +384,7 @@ class MapStep:
                 tail = self._tail_desc() if self._wants_tail() else None
                 loss = mp.step(rays_o, rays_d, gt_depth, gt_color, t_rand, self.w_color, self.w_reg,
                                self._loss_ws('main'), views[0], g_fc=views[1], g_feats=views[2],
-                               far_clamp=far_clamp, overwrite=True, tail=tail)
+                               far_clamp=far_clamp, overwrite=True, tail=tail, ray_grads=rg)
                 self.tail_fused = mp.tail_fused
                 if mp.tail_fused:  # Adam ran inside the reduction: the image is stale, its next scales are not
                     self.opt.step_count += 1
@@ -299,7 +397,7 @@ class MapStep:
                                            ws=self._loss_ws('main'))
             views = self._views['main']
             mp.backward(views[0], g_fc=views[1], g_feats=views[2], g_depth=g_d, g_rgb=g_c, g_sigma=g_s,
-                        overwrite=True)
+                        overwrite=True, ray_grads=rg)
             return self._finish(loss)
         main = torch.cuda.current_stream(dev)
         overlap = self._overlaps(rays_o.shape[0])
@@ -307,20 +405,23 @@ class MapStep:
             self.side = torch.cuda.Stream(dev)
             self.grad2 = torch.zeros_like(self.flat.grad)
             self._views['side'] = self._split(self.grad2)
+        rg2 = None if rg is None else torch.empty_like(rg)  # the regulation chain's ray gradients
         if overlap:
             self.side.wait_stream(main)
             with torch.cuda.stream(self.side):
                 self.grad2.zero_()
-                l_reg = self._regulation_chain(self._views['side'], rays_o, rays_d, gt_depth, t_rand)
+                l_reg = self._regulation_chain(self._views['side'], rays_o, rays_d, gt_depth, t_rand, rg2)
         d, _, c = ren.forward(rays_o, rays_d, gt_depth, far_clamp=far_clamp)
         l_ren, g_d, g_c, _ = map_loss(gt_depth, d, gt_color, c, self.w_color, ws=self._loss_ws('main'))
         views = self._views['main']
-        ren.backward(views[0], g_fc=views[1], g_feats=views[2], g_depth=g_d, g_rgb=g_c)
+        ren.backward(views[0], g_fc=views[1], g_feats=views[2], g_depth=g_d, g_rgb=g_c, ray_grads=rg)
         if overlap:
             main.wait_stream(self.side)
             self.flat.grad.add_(self.grad2)  # render + regulation gradients, a fixed order
         else:
-            l_reg = self._regulation_chain(views, rays_o, rays_d, gt_depth, t_rand)
+            l_reg = self._regulation_chain(views, rays_o, rays_d, gt_depth, t_rand, rg2)
+        if rg is not None:
+            rg.add_(rg2)
         return self._finish(l_ren + l_reg)
 
     def _finish(self, loss):
@@ -337,10 +438,34 @@ class MapStep:
             self.points.invalidate_feats()
         return loss
 
-    def loss(self, rays_o, rays_d, gt_depth, gt_color, t_rand=None, far_clamp=None):
+    def loss(self, rays_o, rays_d, gt_depth, gt_color, t_rand=None, far_clamp=None, camera_tensors=None, idx=None):
         """The Mapper loss through the autograd Renderer API (src/Mapper.py:623-655): the drop-in form
-        of what __call__ computes on its fused path."""
+        of what __call__ computes on its fused path.
+        Bundle adjustment form (src/Mapper.py:567-581): with `camera_tensors` (F,7) and the batch's pixel
+        indices `idx` (F * n, the layout of pnr_window_rays) the rays are built per frame from
+        get_camera_from_tensor through pnr.tracking.rays_from_uv, so the loss reaches the camera tensors
+        (rays_o / rays_d are ignored and may be None); the frames `ba` holds fixed are detached.  The
+        image size and intrinsics are the window sampler's (ba) or else the renderer's."""
         r, dec = self.renderer, self.decoder
+        if camera_tensors is not None:
+            from .common import get_camera_from_tensor
+            from .tracking import rays_from_uv
+            if self.ba is not None:
+                (_, H, W), (fx, fy, cx, cy) = self.ba.sampler.depth.shape, self.ba.sampler.cam
+            else:
+                H, W, fx, fy, cx, cy = r.H, r.W, r.fx, r.fy, r.cx, r.cy
+            F = camera_tensors.shape[0]
+            pix = idx.reshape(F, -1).clamp(0, H * W - 1)
+            ro, rd = [], []
+            for f in range(F):
+                ct = camera_tensors[f]
+                if self.ba is not None and f in self.ba.fixed:
+                    ct = ct.detach()
+                o, d = rays_from_uv((pix[f] % W).float(), torch.div(pix[f], W, rounding_mode='floor').float(),
+                                    get_camera_from_tensor(ct), fx, fy, cx, cy)
+                ro.append(o)
+                rd.append(d)
+            rays_o, rays_d = torch.cat(ro, 0), torch.cat(rd, 0)
         dev = rays_o.device
         d, _, c = r.render_batch_ray(self.c, dec, rays_d, rays_o, dev, 'color', gt_depth, far_clamp=far_clamp)
         m = gt_depth > 0
@@ -504,7 +629,7 @@ class WindowSampler:
         self.generator = generator
         self.device_rng = device_rng
         self.seed = int(seed) & ((1 << 64) - 1)
-        self.idx = None  # the last batch's pixel indices (device_rng)
+        self.idx = None  # the last batch's pixel indices
         if device_rng:
             lib = _lib.load()
             dev = self.depth.device
@@ -516,7 +641,7 @@ class WindowSampler:
         dev = self.depth.device
         N = F * self.n
         if not self.device_rng:
-            idx = torch.randint(H * W, (N,), device=dev, generator=self.generator)
+            idx = self.idx = torch.randint(H * W, (N,), device=dev, generator=self.generator)
             ro, rd, gd, gc = window_rays(idx, self.n, self.c2w, self.depth, self.color, *self.cam)
             t_rand = torch.rand((N, self.n_samples), device=dev, generator=self.generator)
             return ro, rd, gd, gc, t_rand, None

@@ -281,9 +281,10 @@ class TrainPass:
         self.prm, self.ws, self.packed, self.rays = prm, ws, packed, (rays_o, rays_d, far_clamp)
         return out
 
-    def backward(self, grads, g_fc=None, g_feats=None, g_depth=None, g_rgb=None, g_sigma=None):
+    def backward(self, grads, g_fc=None, g_feats=None, g_depth=None, g_rgb=None, g_sigma=None, ray_grads=None):
         """grads: the 11 decoder gradient tensors to add into (contiguous float32); g_fc: the 8 fc_c
-        ones, g_feats: the point features' (with neural points)."""
+        ones, g_feats: the point features' (with neural points).  `ray_grads` = (g_rays_o, g_rays_d)
+        (n,3) float32 buffers: the pass also writes its ray gradients there (need_ray_grads)."""
         lib = _lib.load()
         prm, ws, packed = self.prm, self.ws, self.packed
         rays_o, rays_d, _ = self.rays
@@ -292,17 +293,21 @@ class TrainPass:
         arr = _lib.PtrArray(*[g.data_ptr() for g in grads])
         self.feat.attach(prm, g_feats, g_fc)
         st = _lib.stream_of(dev)
+        g_ro, g_rd = (None, None) if ray_grads is None else ray_grads
+        prm.need_ray_grads = 0 if ray_grads is None else 1
         if self.kind == 'regulation':
             bws = torch.empty(lib.pnr_regulation_bwd_workspace_bytes(ctypes_ref(prm), n), dtype=torch.uint8,
                               device=dev)
             _lib.check(lib.pnr_regulation_bwd(ctypes_ref(prm), _lib.ptr(packed), None, _lib.ptr(rays_o),
-                                              _lib.ptr(rays_d), n, _lib.ptr(g_sigma), arr, None, None, _lib.ptr(ws),
-                                              ws.numel(), _lib.ptr(bws), bws.numel(), st), 'regulation_bwd')
+                                              _lib.ptr(rays_d), n, _lib.ptr(g_sigma), arr, _lib.ptr(g_ro),
+                                              _lib.ptr(g_rd), _lib.ptr(ws), ws.numel(), _lib.ptr(bws), bws.numel(),
+                                              st), 'regulation_bwd')
         else:
             bws = torch.empty(lib.pnr_render_bwd_workspace_bytes(ctypes_ref(prm), n), dtype=torch.uint8, device=dev)
             _lib.check(lib.pnr_render_bwd(ctypes_ref(prm), _lib.ptr(packed), None, _lib.ptr(rays_o), _lib.ptr(rays_d),
-                                          n, _lib.ptr(g_depth), None, _lib.ptr(g_rgb), arr, None, None, _lib.ptr(ws),
-                                          ws.numel(), _lib.ptr(bws), bws.numel(), st), 'render_bwd')
+                                          n, _lib.ptr(g_depth), None, _lib.ptr(g_rgb), arr, _lib.ptr(g_ro),
+                                          _lib.ptr(g_rd), _lib.ptr(ws), ws.numel(), _lib.ptr(bws), bws.numel(), st),
+                       'render_bwd')
         self.ws = self.packed = None  # release the saved activations
 
 
@@ -350,11 +355,15 @@ class MapPass:
                    'map_fwd')
         prm.points = None
         self.prm, self.ws, self.packed, self.rays = prm, ws, packed, (rays_o, rays_d, far_clamp)
+        self.reg_in = (gt_depth, t_rand)
         return depth, var, rgb, sigma
 
-    def backward(self, grads, g_fc=None, g_feats=None, g_depth=None, g_rgb=None, g_sigma=None, overwrite=False):
+    def backward(self, grads, g_fc=None, g_feats=None, g_depth=None, g_rgb=None, g_sigma=None, overwrite=False,
+                 ray_grads=None):
         """Adds the decoder / fc_c gradients into grads / g_fc, or stores them (overwrite: no zero fill
-        needed, pnr_render_params.grads_overwrite); the point-feature gradients always add."""
+        needed, pnr_render_params.grads_overwrite); the point-feature gradients always add.
+        `ray_grads` = (g_rays_o, g_rays_d) (n,3) float32 buffers: pnr_map_bwd_rays also writes the ray
+        gradients there (bundle adjustment)."""
         lib = _lib.load()
         prm, ws, packed = self.prm, self.ws, self.packed
         prm.grads_overwrite = 1 if overwrite else 0
@@ -364,19 +373,28 @@ class MapPass:
         arr = _lib.PtrArray(*[g.data_ptr() for g in grads])
         self.feat.attach(prm, g_feats, g_fc)
         bws = torch.empty(lib.pnr_map_bwd_workspace_bytes(ctypes_ref(prm), n), dtype=torch.uint8, device=dev)
-        _lib.check(lib.pnr_map_bwd(ctypes_ref(prm), _lib.ptr(packed), _lib.ptr(rays_d), n, _lib.ptr(g_depth),
-                                   _lib.ptr(g_rgb), _lib.ptr(g_sigma), arr, _lib.ptr(ws), ws.numel(), _lib.ptr(bws),
-                                   bws.numel(), _lib.stream_of(dev)), 'map_bwd')
+        if ray_grads is not None:
+            gt_depth, t_rand = self.reg_in
+            _lib.check(lib.pnr_map_bwd_rays(ctypes_ref(prm), _lib.ptr(packed), _lib.ptr(rays_d), _lib.ptr(gt_depth),
+                                            _lib.ptr(t_rand), n, _lib.ptr(g_depth), _lib.ptr(g_rgb),
+                                            _lib.ptr(g_sigma), arr, _lib.ptr(ray_grads[0]), _lib.ptr(ray_grads[1]),
+                                            _lib.ptr(ws), ws.numel(), _lib.ptr(bws), bws.numel(),
+                                            _lib.stream_of(dev)), 'map_bwd_rays')
+        else:
+            _lib.check(lib.pnr_map_bwd(ctypes_ref(prm), _lib.ptr(packed), _lib.ptr(rays_d), n, _lib.ptr(g_depth),
+                                       _lib.ptr(g_rgb), _lib.ptr(g_sigma), arr, _lib.ptr(ws), ws.numel(),
+                                       _lib.ptr(bws), bws.numel(), _lib.stream_of(dev)), 'map_bwd')
         self.ws = self.packed = None
 
     def step(self, rays_o, rays_d, gt_depth, gt_color, t_rand, w_color, w_reg, loss_ws, grads, g_fc=None,
-             g_feats=None, far_clamp=None, overwrite=False, tail=None):
+             g_feats=None, far_clamp=None, overwrite=False, tail=None, ray_grads=None):
         """forward + map_loss + backward in ONE C call (pnr_map_step, ABI 13): at batches up to 32,768 rays
         the compositing, the loss and the compositing backward are one fused launch.  Same gradients as
         the three-call form bit for bit; returns the float64 loss (0-dim, on the device).
         `tail` (a _lib.AdamTail): pnr_map_step_adam -- the gradient reduction also takes the Adam step
         and writes the next pack's scales when the call qualifies; `self.tail_fused` says whether it did
-        (False: the caller runs Adam)."""
+        (False: the caller runs Adam).  `ray_grads` = (g_rays_o, g_rays_d): pnr_map_step_rays, the same
+        call (with or without the tail) that also writes the ray gradients."""
         lib = _lib.load()
         r = self.r
         dev = rays_o.device
@@ -401,7 +419,18 @@ class MapPass:
         loss = torch.empty((), dtype=torch.float64, device=dev)
         arr = _lib.PtrArray(*[g.data_ptr() for g in grads])
         self.tail_fused = False
-        if tail is not None:
+        if ray_grads is not None:
+            import ctypes
+            fused = ctypes.c_int32(0)
+            _lib.check(lib.pnr_map_step_rays(ctypes_ref(prm), _lib.ptr(packed), _lib.ptr(rays_o), _lib.ptr(rays_d),
+                                             _lib.ptr(gt_depth), _lib.ptr(gt_color), _lib.ptr(t_rand), n,
+                                             float(w_color), float(w_reg), _lib.ptr(loss), arr, _lib.ptr(ws),
+                                             ws.numel(), _lib.ptr(bws), bws.numel(), _lib.ptr(loss_ws),
+                                             ctypes.byref(tail) if tail is not None else None, ctypes.byref(fused),
+                                             _lib.ptr(ray_grads[0]), _lib.ptr(ray_grads[1]), _lib.stream_of(dev)),
+                       'map_step_rays')
+            self.tail_fused = bool(fused.value)
+        elif tail is not None:
             import ctypes
             fused = ctypes.c_int32(0)
             _lib.check(lib.pnr_map_step_adam(ctypes_ref(prm), _lib.ptr(packed), _lib.ptr(rays_o), _lib.ptr(rays_d),
