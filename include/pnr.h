@@ -215,6 +215,47 @@ int pnr_map_bwd(const pnr_render_params* prm, const float* packed, const float* 
 size_t pnr_points_index_bytes(int64_t n_points, int32_t table_bits);
 /* (Re)builds pts->index from pts->xyz (after any change of positions / cell / origin). */
 int pnr_points_build(const pnr_points* pts, void* stream);
+/* Growing the map from a keyframe's depth (build-defined, as the gather is; tests/points_grow_ref.py
+ * is the spec).  Candidate c = pixel_rank * n_rho + o is pixel (u, v) of the list (`pixels`, flat
+ * v W + u, any order, repeats allowed) or of the `stride` lattice in row-major order, at depth
+ * z = depth[v,u] * (1 + rho[o]) (float32), position p = rays_o + rays_d * z with pnr_get_rays' own
+ * float32 ray.  A candidate is VALID when its depth is finite and > 0 and bound[2a] < p_a <
+ * bound[2a+1] on every axis (a pixel index outside the image is invalid, p = 0); FREE when no
+ * existing point (rows [0, n_points), through pts->index) has (dx dx + dy dy) + dz dz <=
+ * radius_add^2 in unfused float32; with thin > 0 only the smallest candidate index of each voxel
+ * (edge `thin`, the hash origin, the 3 x 21-bit cell identity) is KEPT, with thin == 0 every free
+ * one.  The kept candidates are appended in candidate order at rows [n_points, n_points + n_new) of
+ * xyz_rw (capacity,3) / feats_rw (capacity,32) -- row c of init_feats, or zeros -- up to `capacity`;
+ * no other row is written.  counters_dev: device int64[5] = {candidates, valid, free, kept, dropped
+ * (kept rows beyond capacity)}, n_new = kept - dropped.  The result depends on nothing but the
+ * arguments (integer atomics only, none in the output order).  Requires radius_add <= cell / (2 (1 +
+ * 2^-9)) -- the 2x2x2 probe then covers the ball -- and an index built for the n_points rows;
+ * the caller rebuilds it (pnr_points_build) with the new count afterwards.  At most 2^31 - 1
+ * candidates per call.  pnr_points_add_workspace_bytes(n_cand): n_cand = pixels x n_rho. */
+#define PNR_MAX_RHO 8
+#define PNR_ADD_VALID 1
+#define PNR_ADD_FREE 2
+#define PNR_ADD_KEPT 4
+typedef struct pnr_points_add {
+  const float* depth;       /* (H,W) float32, device                                          */
+  const float* c2w;         /* (4,4) float32 row-major, device                                */
+  int32_t H, W;
+  float fx, fy, cx, cy;
+  const int64_t* pixels;    /* (n_pixels) flat pixel indices, device; NULL = the stride lattice */
+  int64_t n_pixels;         /* length of `pixels` (ignored when NULL)                         */
+  int32_t stride;           /* >= 1: pixels (0, s, 2s, ...) of both axes when `pixels` is NULL */
+  int32_t n_rho;            /* 1..PNR_MAX_RHO                                                 */
+  float rho[PNR_MAX_RHO];   /* relative depth offsets                                         */
+  float radius_add;         /* > 0                                                            */
+  float thin;               /* voxel edge of the thinning, 0 = none                           */
+  float bound[6];           /* x0,x1,y0,y1,z0,z1 (float32: the test runs in the positions' type) */
+  const float* init_feats;  /* (n_cand,32) float32 initial features per candidate, NULL = zeros */
+  float* cand_xyz;          /* out, optional: (n_cand,3) candidate positions                  */
+  uint8_t* cand_flags;      /* out, optional: (n_cand) PNR_ADD_* bits                         */
+} pnr_points_add;
+size_t pnr_points_add_workspace_bytes(int64_t n_cand);
+int pnr_points_add_frame(const pnr_points* pts, int64_t capacity, float* xyz_rw, float* feats_rw,
+                         const pnr_points_add* args, void* ws, size_t ws_bytes, int64_t* counters_dev, void* stream);
 /* Standalone gather: c (P,32) float32 for float64 points p (P,3).  idx (P,k) int32 (-1 = none)
  * and w (P,k) float32 normalised weights are written when non-NULL (needed by the backward).
  * ws: pnr_point_gather_workspace_bytes(P) bytes (work list of samples with candidates). */

@@ -1300,6 +1300,22 @@ int pnr_points_build(const pnr_points* pts, void* stream) {
   return launch_points_build(*pts, (hipStream_t)stream);
 }
 
+size_t pnr_points_add_workspace_bytes(int64_t n_cand) {
+  return n_cand < 0 || n_cand > 0x7FFFFFFFll ? 0 : points_add_workspace_bytes(n_cand);
+}
+
+int pnr_points_add_frame(const pnr_points* pts, int64_t capacity, float* xyz_rw, float* feats_rw,
+                         const pnr_points_add* args, void* ws, size_t ws_bytes, int64_t* counters_dev, void* stream) {
+  if (!pts || !args || !xyz_rw || !feats_rw || !counters_dev || pts->n_points < 0 || capacity < pts->n_points ||
+      pts->table_bits < 10 || pts->table_bits > 24 || !(pts->cell > 0.f) || (pts->n_points > 0 && !pts->index))
+    return PNR_E_ARG;
+  if (!args->depth || !args->c2w || !(args->radius_add > 0.f) || !(args->thin >= 0.f) ||
+      !(args->radius_add * 2.0f * (1.0f + 1.0f / 512.0f) <= pts->cell))  // the 2x2x2 probe covers the ball
+    return PNR_E_ARG;
+  if (points_add_candidates(*args) < 0) return PNR_E_ARG;
+  return launch_points_add(*pts, capacity, xyz_rw, feats_rw, *args, ws, ws_bytes, counters_dev, (hipStream_t)stream);
+}
+
 size_t pnr_point_gather_workspace_bytes(int64_t P) { return P < 0 ? 0 : gather_workspace_bytes(P); }
 
 int pnr_point_gather(const pnr_points* pts, const double* p, int64_t P, float* c, int32_t* idx, float* w, void* ws,

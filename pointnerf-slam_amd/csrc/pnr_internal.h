@@ -328,6 +328,14 @@ struct IndexView {
 };
 IndexView index_view(void* base, int64_t M, int32_t bits, size_t* bytes);
 int launch_points_build(const pnr_points& pts, hipStream_t st);
+// out[0..n] = exclusive scan of in[0..n), out[n] = total (n > 0).  scratch: scan_scratch_ints(n) ints.
+int64_t scan_scratch_ints(int64_t n);
+int scan_exclusive(const int32_t* in, int32_t* out, int64_t n, int32_t* scratch, hipStream_t st);
+// the insertion pass (points_grow.hip): candidates of one frame -> appended rows [n, n + n_new)
+int64_t points_add_candidates(const pnr_points_add& a);  // candidate count of a call, -1 = bad arguments
+size_t points_add_workspace_bytes(int64_t n_cand);
+int launch_points_add(const pnr_points& pts, int64_t capacity, float* xyz, float* feats, const pnr_points_add& a,
+                      void* ws, size_t ws_bytes, int64_t* counters, hipStream_t st);
 // c rows [0, rows): points [0, P) gathered, rows [P, rows) zeroed
 // ws: gather_workspace_bytes(P) (work list of the two-pass gather)
 size_t gather_workspace_bytes(int64_t P);

@@ -33,39 +33,11 @@
 #include <type_traits>
 
 #include "pnr_internal.h"
+#include "points_hash.h"
 
 namespace pnr {
 
-#define PNR_FP_STRICT _Pragma("clang fp contract(off)")
-
 namespace {
-
-struct HashGrid {
-  float o0, o1, o2;
-  float inv;       // 1 / cell
-  uint32_t mask;   // T - 1
-  uint32_t omask;  // occupancy bits - 1
-};
-
-int occ_bits_log2(int32_t bits) { return bits + 6 < 26 ? bits + 6 : 26; }
-
-HashGrid make_grid(const pnr_points& p) {
-  HashGrid g;
-  g.o0 = p.origin[0];
-  g.o1 = p.origin[1];
-  g.o2 = p.origin[2];
-  g.inv = 1.0f / p.cell;
-  g.mask = (uint32_t)((1ll << p.table_bits) - 1);
-  g.omask = (uint32_t)((1ll << occ_bits_log2(p.table_bits)) - 1);
-  return g;
-}
-
-__device__ __forceinline__ int cell_coord(float x, float o, float inv) {
-  PNR_FP_STRICT
-  float f = floorf((x - o) * inv);
-  f = fminf(fmaxf(f, -1.0e9f), 1.0e9f);  // far-away / non-finite samples: any cell, never UB
-  return (int)f;
-}
 
 // half of its cell a coordinate lies in (0 lower, 1 upper), from the same f32 value as cell_coord
 __device__ __forceinline__ int sub_bit(float x, float o, float inv) {
@@ -78,26 +50,6 @@ __device__ __forceinline__ int sub_bit(float x, float o, float inv) {
 __device__ __forceinline__ int sub_index(float x, float y, float z, float o0, float o1, float o2, float inv) {
   return sub_bit(x, o0, inv) | (sub_bit(y, o1, inv) << 1) | (sub_bit(z, o2, inv) << 2);
 }
-
-// lower of the two cells per axis that cover [x - reach, x + reach] when cell >= 2 reach
-__device__ __forceinline__ void base_cell(float x, float o, float inv, int& b) {
-  PNR_FP_STRICT
-  float t = (x - o) * inv;
-  t = fminf(fmaxf(t, -1.0e9f), 1.0e9f);
-  const float f = floorf(t);
-  b = (int)f - (t - f < 0.5f ? 1 : 0);
-}
-
-__device__ __forceinline__ uint32_t cell_hash(int cx, int cy, int cz, uint32_t mask) {
-  return (((uint32_t)cx * 73856093u) ^ ((uint32_t)cy * 19349663u) ^ ((uint32_t)cz * 83492791u)) & mask;
-}
-
-// exact cell identity: 3 x 21-bit two's complement (scenes stay far below 2^20 cells per axis)
-__device__ __forceinline__ uint64_t cell_key(int cx, int cy, int cz) {
-  return (uint64_t)((uint32_t)cx & 0x1FFFFFu) | ((uint64_t)((uint32_t)cy & 0x1FFFFFu) << 21) |
-         ((uint64_t)((uint32_t)cz & 0x1FFFFFu) << 42);
-}
-constexpr uint64_t kCollision = 1ull << 63;
 
 // (d2, index) as one float64 whose order is the lexicographic order: d2 >= 0 has monotone float
 // bits; +2^20 on the high word keeps every key a normal double (no denormal flushing)
@@ -117,7 +69,7 @@ __device__ __forceinline__ int key_id(double k) { return (int)(uint32_t)(uint64_
 // ---------------------------------------------------------------------------------------------
 static inline size_t a256(size_t x) { return (x + 255) / 256 * 256; }
 
-static int64_t scan_scratch_ints(int64_t n) {
+int64_t scan_scratch_ints(int64_t n) {
   int64_t tot = 0;
   while (true) {
     const int64_t nb = (n + 1023) / 1024;
@@ -241,7 +193,7 @@ __global__ __launch_bounds__(1024) void k_scan_small(const int32_t* __restrict__
 }
 
 // out[0..n] = exclusive scan of in[0..n), out[n] = total.  scratch: scan_scratch_ints(n) ints.
-static int scan_exclusive(const int32_t* in, int32_t* out, int64_t n, int32_t* scratch, hipStream_t st) {
+int scan_exclusive(const int32_t* in, int32_t* out, int64_t n, int32_t* scratch, hipStream_t st) {
   if (n > 0 && n <= kScanSmall) {
     hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, in, out, n);
     return hip_status(hipGetLastError());

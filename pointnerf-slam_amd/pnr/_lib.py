@@ -53,6 +53,20 @@ class Points(ctypes.Structure):
     ]
 
 
+MAX_RHO = 8  # include/pnr.h PNR_MAX_RHO
+ADD_VALID, ADD_FREE, ADD_KEPT = 1, 2, 4  # include/pnr.h PNR_ADD_*
+
+
+class PointsAdd(ctypes.Structure):
+    """Mirror of `pnr_points_add` (include/pnr.h)."""
+    _fields_ = [
+        ('depth', c_void_p), ('c2w', c_void_p), ('H', c_int32), ('W', c_int32), ('fx', c_float), ('fy', c_float),
+        ('cx', c_float), ('cy', c_float), ('pixels', c_void_p), ('n_pixels', c_int64), ('stride', c_int32),
+        ('n_rho', c_int32), ('rho', c_float * MAX_RHO), ('radius_add', c_float), ('thin', c_float),
+        ('bound', c_float * 6), ('init_feats', c_void_p), ('cand_xyz', c_void_p), ('cand_flags', c_void_p),
+    ]
+
+
 class RenderParams(ctypes.Structure):
     """Mirror of `pnr_render_params` (include/pnr.h)."""
     _fields_ = [
@@ -165,6 +179,9 @@ _SIGS = {
                                     c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'pnr_points_index_bytes': (c_size_t, [c_int64, c_int32]),
     'pnr_points_build': (ctypes.c_int, [PPoints, c_void_p]),
+    'pnr_points_add_workspace_bytes': (c_size_t, [c_int64]),
+    'pnr_points_add_frame': (ctypes.c_int, [PPoints, c_int64, c_void_p, c_void_p, ctypes.POINTER(PointsAdd), c_void_p,
+                                            c_size_t, c_void_p, c_void_p]),
     'pnr_point_gather_workspace_bytes': (c_size_t, [c_int64]),
     'pnr_point_gather': (ctypes.c_int, [PPoints, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                         c_void_p]),

@@ -29,8 +29,11 @@ def c_state(c):
     out = {}
     for key, v in (c or {}).items():
         if isinstance(v, NeuralPoints):
-            d = {'xyz': v.xyz.detach().cpu(), 'feats': v.feats.detach().cpu()}
+            n = v.n_points  # a cloud with a capacity: the live rows, and the capacity to restore it with
+            d = {'xyz': v.xyz[:n].detach().cpu(), 'feats': v.feats[:n].detach().cpu()}
             d.update({f: getattr(v, f) for f in _PT_FIELDS})
+            if v.capacity is not None:
+                d['capacity'] = v.capacity
             out[key] = d
         elif isinstance(v, torch.Tensor):
             out[key] = v.detach().cpu()
@@ -44,7 +47,7 @@ def c_from_state(cs, device='cpu'):
     out = {}
     for key, v in (cs or {}).items():
         if isinstance(v, dict) and 'xyz' in v and 'feats' in v:
-            kw = {f: v[f] for f in _PT_FIELDS if f in v}
+            kw = {f: v[f] for f in _PT_FIELDS + ('capacity',) if f in v}
             out[key] = NeuralPoints(v['xyz'].to(device), v['feats'].to(device), c_dim=v['feats'].shape[1], **kw)
         else:
             out[key] = v

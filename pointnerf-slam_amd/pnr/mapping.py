@@ -234,6 +234,11 @@ class MapStep:
         if points is not None:
             params.append(points.feats)
         self.flat = FlatParams(params)
+        # A cloud with a capacity (NeuralPoints.add_frame) steps every row of `feats`, live or not: the
+        # feature gradient view is zeroed every step, a row that is not live is no sample's neighbour and
+        # keeps a zero gradient, and Adam with g = m = v = 0 leaves it bit-identical.  One deviation from
+        # a per-row optimiser: a row that becomes live later meets Adam's running step count (its bias
+        # corrections), not a fresh one.
         segs = [(0, n_dec, lr)]
         self.n_dec = n_dec
         self.shard = points is not None and ddp is not None and getattr(ddp, 'shard_points', False)
@@ -529,6 +534,8 @@ class MapGraph:
                 grouped = carry_scales and isinstance(batch_fn, WindowSampler) and batch_fn.device_rng
                 pack = mstep.head_pack() if grouped else None
                 return mstep(*(batch_fn(pack=pack) if pack is not None else batch_fn()))
+        # the descriptor's n_points and the index are captured by value: a grown cloud needs a new graph
+        self.n_points = None if mstep.points is None else mstep.points.n_points
         mstep.opt.use_device_step()
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -548,6 +555,9 @@ class MapGraph:
         """Copy the batch into the static inputs (a tensor that IS the static buffer -- the caller
         wrote its batch into `self.inputs` directly -- is not copied), replay, return the loss.  With a
         captured `batch_fn`, just replay."""
+        if self.n_points is not None and self.mstep.points.n_points != self.n_points:
+            raise RuntimeError(f'pnr.MapGraph: the cloud grew from {self.n_points} to {self.mstep.points.n_points} '
+                               'points since the capture (NeuralPoints.add_frame): make a new MapGraph')
         if self.batch_fn is None:
             for dst, src in zip(self.inputs, (rays_o, rays_d, gt_depth, gt_color, t_rand)):
                 if src.data_ptr() != dst.data_ptr():
