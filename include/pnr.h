@@ -265,12 +265,20 @@ int pnr_point_gather(const pnr_points* pts, const double* p, int64_t P, float* c
 /* Backward of pnr_point_gather: g_c (P,32) -> pts->g_feats (+=, when non-NULL) and g_p (P,3)
  * (written, when non-NULL: dL/dp through the weights).  ws: pnr_point_gather_bwd_workspace_bytes
  * (ABI 10).  The feature gradient is DETERMINISTIC (ABI 10): every term w_k dL/dc is rounded once to
- * an int64 multiple of 2^-s (s from max |dL/dc| of the call and the guard bits ceil(log2(P+1)), so
- * no sum overflows), the terms are added exactly with 64-bit integer atomics, and the sum is
- * converted once into g_feats.  Any order of the additions gives the same bits.  The absolute error
- * of an element is at most (its term count) x 2^-(63 - guard) x max |dL/dc|: fp32-class for any
- * element above ~2^-14 of the largest term.  A non-finite dL/dc makes every element of the feature
- * rows the call's samples name NaN; rows no sample names are left untouched (ABI 12). */
+ * an int64 multiple of 2^-s, the terms are added exactly with 64-bit integer atomics, and the sum is
+ * converted once into g_feats.  Any order of the additions gives the same bits.  The fixed point, in
+ * full (tests/gather_bwd_model.py restates it): a sample row takes part when idx[row][0] >= 0; guard
+ * = the smallest integer >= 1 with 2^guard > P, at most 40 (ceil(log2(P+1)) for P >= 1); gmax = max
+ * |dL/dc| over every channel of the rows that take part; e = its frexp exponent (gmax = m 2^e, 0.5 <=
+ * m < 1); s = 62 - guard - e, or 0 when gmax is 0, so |term| 2^s < 2^(62 - guard) and no sum of P
+ * terms overflows.  A term is rint(ldexp(fl32(w_k dL/dc), s)): the float32 product, scaled exactly,
+ * rounded half to even; the result g_feats = fl32(g_feats + fl32(float64(sum) 2^-s)).  The absolute
+ * error of an element before that conversion is at most (its term count) x 2^-(s + 1) = (count) x
+ * 2^-(63 - guard) x 2^e, under (count) x 2^-(62 - guard) x max |dL/dc|: fp32-class for any element
+ * above ~2^-14 of the largest term.  A non-finite dL/dc in a row that takes part makes every element
+ * of the feature rows the call's samples name NaN; rows no sample names are left untouched (ABI 12)
+ * in sparse and dense calls alike (a dense call, P k >= 4 n_points, adds +0 to them: only a -0 there
+ * changes, to +0), and a dL/dc row without neighbours has no effect at all. */
 size_t pnr_point_gather_bwd_workspace_bytes(const pnr_points* pts, int64_t P);
 int pnr_point_gather_bwd(const pnr_points* pts, const double* p, int64_t P, const int32_t* idx, const float* w,
                          const float* c, const float* g_c, float* g_p, void* ws, size_t ws_bytes, void* stream);

@@ -1113,9 +1113,31 @@ __global__ __launch_bounds__(256) void k_gather_bwd(GatherBwdArgs a) {
   const int ch = threadIdx.x & 31, half = threadIdx.x >> 5;  // 8 half-waves per block
   const int R = a.run, per = 8 * R;  // items per half-wave run / per block task
   const int64_t nchunk = (a.wl.cap + per - 1) / per;
-  const int fs = a.g_feats ? fx_shift(*a.gmax, a.guard) : 0;
+  const uint32_t gmb = a.g_feats ? *a.gmax : 0u;
+  const int fs = fx_shift(gmb, a.guard);
+  // a non-finite max |dL/dc| (uniform over the launch): no term is formed; every (row, neighbour) pair
+  // adds 1 instead, so exactly the rows some sample names end with non-zero accumulators (at most P <
+  // 2^guard per element) and k_gather_bwd_fin finds them, in a dense call too
+  const bool bad = gmb >= 0x7F800000u;
+  const bool sums = a.g_feats && !bad;
   unsigned long long* facc = reinterpret_cast<unsigned long long*>(a.facc);
   uint32_t nfl = 0;  // flushes of this half-wave (uniform over it)
+  if (bad) {  // the marking pass, over the same rows per half-wave as the loop below (which adds nothing then)
+    for (int64_t task = blockIdx.x; task < kLists * nchunk; task += gridDim.x) {
+      const int rl = (int)(task % kLists);
+      const int64_t n_work = (int64_t)a.wl.cnt[rl * 32];
+      const int64_t t0 = task / kLists * per + (int64_t)R * half, te = t0 + R < n_work ? t0 + R : n_work;
+      for (int64_t t = t0; t < te; ++t) {
+        const int64_t p = __float_as_int(a.wl.items[rl * a.wl.cap + t].w);
+        for (int kk = 0; kk < a.k; ++kk) {
+          const int id = a.idx[p * a.k + kk];
+          if (id < 0) continue;
+          atomicAdd(facc + (int64_t)id * 32 + ch, 1ull);
+          ++nfl;
+        }
+      }
+    }
+  }
   for (int64_t task = blockIdx.x; task < kLists * nchunk; task += gridDim.x) {
     const int rl = (int)(task % kLists);
     const int64_t j0 = task / kLists * per;
@@ -1175,7 +1197,7 @@ __global__ __launch_bounds__(256) void k_gather_bwd(GatherBwdArgs a) {
 #pragma unroll
         for (int kk = 0; kk < PNR_MAX_K; ++kk) dots[kk] = g * f[kk];
       }
-      if (a.g_feats) {
+      if (sums) {
         long long cur[PNR_MAX_K];
 #pragma unroll
         for (int kk = 0; kk < PNR_MAX_K; ++kk) cur[kk] = id[kk] >= 0 ? fx_term(wn[kk] * g, fs) : 0;
@@ -1255,8 +1277,9 @@ __global__ __launch_bounds__(256) void k_gather_bwd(GatherBwdArgs a) {
 }
 
 // g_feats += facc 2^-s (4 values per thread) on the rows some sample named (the others received no
-// term: left as they are, their accumulators never zeroed); a non-finite max |dL/dc| makes the
-// elements of those rows NaN
+// term: left as they are, their accumulators never zeroed, or zero in a dense call); a non-finite max
+// |dL/dc| makes the elements of those rows NaN: the accumulators then hold the number of samples that
+// name the row (k_gather_bwd), zero on the rows a dense call converts without any sample naming them
 __global__ __launch_bounds__(256) void k_gather_bwd_fin(const long long* __restrict__ facc, float* __restrict__ g,
                                                        int64_t n, const uint32_t* __restrict__ gmax, int guard,
                                                        const uint32_t* __restrict__ touched) {
@@ -1267,19 +1290,20 @@ __global__ __launch_bounds__(256) void k_gather_bwd_fin(const long long* __restr
   const uint32_t gb = *gmax;
   const int s = fx_shift(gb, guard);
   const bool bad = gb >= 0x7F800000u;
+  const float qnan = __int_as_float(0x7FC00000);
   // g may be a view at any float offset of a flat gradient buffer: 16-B accesses only when aligned
   if (i + 4 <= n && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
     const longlong2 v0 = *reinterpret_cast<const longlong2*>(facc + i);
     const longlong2 v1 = *reinterpret_cast<const longlong2*>(facc + i + 2);
     float4 o = *reinterpret_cast<float4*>(g + i);
-    o.x += bad ? __int_as_float(0x7FC00000) : (float)ldexp((double)v0.x, -s);
-    o.y += bad ? __int_as_float(0x7FC00000) : (float)ldexp((double)v0.y, -s);
-    o.z += bad ? __int_as_float(0x7FC00000) : (float)ldexp((double)v1.x, -s);
-    o.w += bad ? __int_as_float(0x7FC00000) : (float)ldexp((double)v1.y, -s);
+    o.x += bad ? (v0.x != 0 ? qnan : 0.f) : (float)ldexp((double)v0.x, -s);
+    o.y += bad ? (v0.y != 0 ? qnan : 0.f) : (float)ldexp((double)v0.y, -s);
+    o.z += bad ? (v1.x != 0 ? qnan : 0.f) : (float)ldexp((double)v1.x, -s);
+    o.w += bad ? (v1.y != 0 ? qnan : 0.f) : (float)ldexp((double)v1.y, -s);
     *reinterpret_cast<float4*>(g + i) = o;
   } else {
     const int64_t e = i + 4 < n ? i + 4 : n;
-    for (int64_t j = i; j < e; ++j) g[j] += bad ? __int_as_float(0x7FC00000) : (float)ldexp((double)facc[j], -s);
+    for (int64_t j = i; j < e; ++j) g[j] += bad ? (facc[j] != 0 ? qnan : 0.f) : (float)ldexp((double)facc[j], -s);
   }
 }
 
