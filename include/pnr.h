@@ -560,6 +560,49 @@ int pnr_marching_cubes_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz
                             int64_t sz, double level, const double* origin, const double* spacing, const void* ws,
                             size_t ws_bytes, double* vertices, int32_t* faces, void* stream);
 
+/* ---- mesh bound from the keyframes (src/utils/Mesher.py:214-279, applied at :426-433 / :475-485;
+ * additions to ABI 14) --------------------------------------------------------------------------
+ * The reference bounds the mesh by the convex hull of a TSDF surface fused from the keyframes' depth
+ * (Mesher.py:214-279).  Here the hull is taken over the point set P itself, and the device supplies
+ * the three passes over P or over the grid; the combinatorics run on the host (pnr/bound.py).
+ * P, with its index space:
+ *   depth pixels   keyframe k < K, pixel (v, u) of the `stride` lattice (v, u multiples of stride), depth
+ *                  d finite, 0 < d <= depth_trunc (Mesher.py:253's depth_trunc): index k H W + v W + u,
+ *                  position pnr_points_add_frame's with rho = 0 (the same device function): the float32
+ *                  ray of pnr_get_rays, p = rays_o + rays_d d, unfused
+ *   extra points   n_extra float32 rows (the camera centres c2w[:3,3], Mesher.py:262-267): index
+ *                  K H W + e; a row with a NaN coordinate is invalid
+ * K H W + n_extra < 2^31. */
+typedef struct pnr_bound_frames {
+  const float* depth;      /* (K,H,W) float32, device                                          */
+  const float* c2w;        /* (K,4,4) float32 row-major, device                                */
+  int32_t K, H, W, stride; /* K >= 0, stride >= 1                                              */
+  float fx, fy, cx, cy, depth_trunc;
+  const float* extra_xyz;  /* (n_extra,3) float32, device; NULL when n_extra == 0              */
+  int64_t n_extra;
+} pnr_bound_frames;
+/* The support function of P (the pass quickhull makes per round, Mesher.py:270's hull): for each of the
+ * D <= pnr_bound_support_max_dirs() float32 directions n, h = max over the valid points of
+ * (x nx + y ny) + z nz in unfused float32 (a NaN product never wins) and arg = the smallest index that
+ * attains it; no valid point: h = -inf, arg = -1, and the call still returns 0.  Max and min-index
+ * commute, so the result depends on nothing but the arguments: persistent workgroups write per-workgroup
+ * (value, index) rows with plain stores and one fixed-order launch reduces them; no float atomics.
+ * ws: pnr_bound_support_workspace_bytes(frames, D) bytes (0 for bad arguments). */
+int32_t pnr_bound_support_max_dirs(void);
+size_t pnr_bound_support_workspace_bytes(const pnr_bound_frames* frames, int32_t n_dirs);
+int pnr_bound_support(const pnr_bound_frames* frames, const float* dirs, int32_t D, float* h, int64_t* arg,
+                      void* ws, size_t ws_bytes, void* stream);
+/* Positions (n,3) float32 of the points of P with the given indices (the hull's vertices, Mesher.py:270);
+ * an index outside [0, K H W + n_extra), off the lattice or of an invalid point gives a NaN row. */
+int pnr_bound_points(const pnr_bound_frames* frames, const int64_t* idx, int64_t n, float* xyz, void* stream);
+/* The hull mask of Mesher.py:426 (`mesh_bound.contains`): inside[i] = 1 when (x a + y b) + z c <= d in
+ * unfused float64 for every plane (a, b, c, d) of `planes` (F,4) float64 (float32 points are widened
+ * first), else 0; F = 0 gives all ones. */
+int pnr_bound_contains_f32(const float* p, int64_t P, const double* planes, int32_t F, uint8_t* inside,
+                           void* stream);
+int pnr_bound_contains_f64(const double* p, int64_t P, const double* planes, int32_t F, uint8_t* inside,
+                           void* stream);
+
 /* ---- diagnostics (not on the reference API) ----------------------------------------------- */
 /* Kernel timing: while enabled, every launch of the timed kernels is bracketed by hipEvents on
  * its own stream.  pnr_timing_read synchronises those events and returns, for `kernel`

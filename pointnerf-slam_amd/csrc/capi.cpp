@@ -86,6 +86,12 @@ int launch_mc_count(const float*, int64_t, int64_t, int64_t, int64_t, int64_t, i
                     int64_t*, hipStream_t);
 int launch_mc_emit(const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, double, const double*,
                    const double*, const void*, double*, int32_t*, hipStream_t);
+int bound_support_max_dirs();
+size_t bound_support_workspace_bytes(const pnr_bound_frames&, int32_t);
+int launch_bound_support(const pnr_bound_frames&, const float*, int32_t, float*, int64_t*, void*, size_t, hipStream_t);
+int launch_bound_points(const pnr_bound_frames&, const int64_t*, int64_t, float*, hipStream_t);
+int launch_bound_contains_f32(const float*, int64_t, const double*, int32_t, uint8_t*, hipStream_t);
+int launch_bound_contains_f64(const double*, int64_t, const double*, int32_t, uint8_t*, hipStream_t);
 
 }  // namespace pnr
 
@@ -1589,6 +1595,34 @@ int pnr_marching_cubes_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz
   if (ws_bytes < pnr_marching_cubes_workspace_bytes(nx, ny, nz)) return PNR_E_WORKSPACE;
   return launch_mc_emit(vol, nx, ny, nz, sx, sy, sz, level, origin, spacing, ws, vertices, faces,
                         (hipStream_t)stream);
+}
+
+// ---- mesh bound from the keyframes (bound.hip; Mesher.py:214-279) -------------------------------------
+int32_t pnr_bound_support_max_dirs(void) { return bound_support_max_dirs(); }
+
+size_t pnr_bound_support_workspace_bytes(const pnr_bound_frames* frames, int32_t n_dirs) {
+  return frames ? bound_support_workspace_bytes(*frames, n_dirs) : 0;
+}
+
+int pnr_bound_support(const pnr_bound_frames* frames, const float* dirs, int32_t D, float* h, int64_t* arg, void* ws,
+                      size_t ws_bytes, void* stream) {
+  if (!frames) return PNR_E_ARG;
+  return launch_bound_support(*frames, dirs, D, h, arg, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int pnr_bound_points(const pnr_bound_frames* frames, const int64_t* idx, int64_t n, float* xyz, void* stream) {
+  if (!frames) return PNR_E_ARG;
+  return launch_bound_points(*frames, idx, n, xyz, (hipStream_t)stream);
+}
+
+int pnr_bound_contains_f32(const float* p, int64_t P, const double* planes, int32_t F, uint8_t* inside,
+                           void* stream) {
+  return launch_bound_contains_f32(p, P, planes, F, inside, (hipStream_t)stream);
+}
+
+int pnr_bound_contains_f64(const double* p, int64_t P, const double* planes, int32_t F, uint8_t* inside,
+                           void* stream) {
+  return launch_bound_contains_f64(p, P, planes, F, inside, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -3,8 +3,9 @@
 // The reference has no neural-point stage; Point-SLAM's Mapper calls this step add_neural_points.  It is
 // build-defined: include/pnr.h (pnr_points_add_frame) states the rules and tests/points_grow_ref.py
 // restates them on the CPU.  One call, stream-ordered, no host read:
-//   k_add_candidates  one thread per candidate (pixel x depth offset): depth load, make_ray (the ray
-//                     k_get_rays builds), the position, the bound test, and the test against the
+//   k_add_candidates  one thread per candidate (pixel x depth offset): depth load, backproject
+//                     (window_sample.h: the ray k_get_rays builds and the position on it; shared with
+//                     the mesh bound, bound.hip), the bound test, and the test against the
 //                     existing points through the cloud's index -- base_cell, the 8 bucket headers of
 //                     the 2x2x2 probe block (own bucket or colliding bucket; a foreign bucket is not
 //                     read), the buckets' points until the first one inside the ball.  Coalesced
@@ -122,11 +123,7 @@ __global__ __launch_bounds__(256) void k_add_candidates(AddArgs a) {
 #pragma unroll
       for (int k = 1; k < PNR_MAX_RHO; ++k) rho = o == k ? a.a.rho[k] : rho;
       const float z = d * (1.0f + rho);
-      float ro[3], rd[3];
-      make_ray((float)u, (float)v, a.a.fx, a.a.fy, a.a.cx, a.a.cy, a.a.c2w, 4, ro, rd);
-      px = ro[0] + rd[0] * z;
-      py = ro[1] + rd[1] * z;
-      pz = ro[2] + rd[2] * z;
+      backproject((float)u, (float)v, z, a.a.fx, a.a.fy, a.a.cx, a.a.cy, a.a.c2w, px, py, pz);
       valid = d > 0.f && d <= 3.402823466e+38f && px > a.a.bound[0] && px < a.a.bound[1] && py > a.a.bound[2] &&
               py < a.a.bound[3] && pz > a.a.bound[4] && pz < a.a.bound[5];
     }

@@ -30,6 +30,18 @@ __device__ __forceinline__ void make_ray(float i, float j, float fx, float fy, f
   }
 }
 
+// World position of pixel (u, v) at depth z along make_ray's float32 ray: p = rays_o + rays_d z, unfused.
+// One statement of it for the map growth (points_grow.hip k_add_candidates) and the mesh bound (bound.hip).
+__device__ __forceinline__ void backproject(float u, float v, float z, float fx, float fy, float cx, float cy,
+                                            const float* __restrict__ c2w, float& px, float& py, float& pz) {
+#pragma clang fp contract(off)
+  float ro[3], rd[3];
+  make_ray(u, v, fx, fy, cx, cy, c2w, 4, ro, rd);
+  px = ro[0] + rd[0] * z;
+  py = ro[1] + rd[1] * z;
+  pz = ro[2] + rd[2] * z;
+}
+
 // A mapping iteration's whole window batch in ONE launch, drawn on the device: the uniform pixels
 // (torch.randint(H*W) per ray in Mapper.py:560-606's get_samples), the regulation jitter t_rand
 // (torch.rand, Renderer.py:293), the rays and gt of k_window_rays, and the batch far clamp

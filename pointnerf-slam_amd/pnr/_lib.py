@@ -88,6 +88,16 @@ class AdamTail(ctypes.Structure):
     ]
 
 
+class BoundFrames(ctypes.Structure):
+    """Mirror of `pnr_bound_frames` (include/pnr.h)."""
+    _fields_ = [
+        ('depth', c_void_p), ('c2w', c_void_p), ('K', c_int32), ('H', c_int32), ('W', c_int32), ('stride', c_int32),
+        ('fx', c_float), ('fy', c_float), ('cx', c_float), ('cy', c_float), ('depth_trunc', c_float),
+        ('extra_xyz', c_void_p), ('n_extra', c_int64),
+    ]
+
+
+PBoundFrames = ctypes.POINTER(BoundFrames)
 PtrArray = c_void_p * N_PARAMS
 FcPtrArray = c_void_p * N_FC_PARAMS
 PPoints = ctypes.POINTER(Points)
@@ -210,6 +220,13 @@ _SIGS = {
     'pnr_marching_cubes_emit': (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
                                                ctypes.c_double, ctypes.c_double * 3, ctypes.c_double * 3, c_void_p,
                                                c_size_t, c_void_p, c_void_p, c_void_p]),
+    'pnr_bound_support_max_dirs': (c_int32, []),
+    'pnr_bound_support_workspace_bytes': (c_size_t, [PBoundFrames, c_int32]),
+    'pnr_bound_support': (ctypes.c_int, [PBoundFrames, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
+                                         c_void_p]),
+    'pnr_bound_points': (ctypes.c_int, [PBoundFrames, c_void_p, c_int64, c_void_p, c_void_p]),
+    'pnr_bound_contains_f32': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
+    'pnr_bound_contains_f64': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
     'pnr_timing_enable': (ctypes.c_int, [ctypes.c_int]),
     'pnr_timing_read': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_int64), ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(c_int64)]),

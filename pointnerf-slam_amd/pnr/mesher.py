@@ -17,12 +17,21 @@ host libraries for it (skimage, trimesh, open3d) are not importable on this stac
     skimage's default winding, a generated crack-free case table (tools/gen_mc_table.py);
   * `clean_mesh`: the all-unseen face cull, connected components, the small-component filter or
     the largest component, and the compaction (:469-510), in torch ops on the device;
+  * `get_bound_from_frames` (:214-279): the convex hull of what the keyframes saw as a `FrameBound`
+    -- the support function of the back-projected depth pixels, the positions of chosen points and the
+    containment test on the device (csrc/bound.hip), the quickhull between them on the host
+    (pnr/bound.py) -- applied by get_mesh with `mesh_bound_mask='frames'`;
   * `write_ply`, and `Mesher.get_mesh` that strings everything together.
-Two stated deviations.  Components are taken over shared VERTICES, trimesh.split takes them over
-shared edges: the two differ only where components touch at a single vertex.  And
-`get_bound_from_frames` (:214-279: open3d's TSDF volume plus a convex hull) is out of scope: get_mesh
-takes an optional `mesh_bound_mask` instead, and without it applies no hull mask (eval_points already
-returns 100 outside the scene bound).
+Stated deviations.  Components rule: components are taken over shared VERTICES, trimesh.split takes
+them over shared edges: the two differ only where components touch at a single vertex.  Depth pixels,
+not a TSDF surface: the reference's hull is taken over the vertices of an open3d TSDF surface (voxel
+4 scale / 512) fused from the depth maps, ours over the valid depth pixels themselves and the camera
+centres; the two hulls differ by the order of that voxel, and parity with open3d is unpinned, as for
+`vertex_normals`.  A hull to a tolerance: refinement stops when no point lies more than eps / 2
+(default eps = 4 scale / 512) outside a facet, and each facet's plane is then moved out to the measured
+support of the points plus a rounding guard, so hull(V) <= hull(P) <= H for the result H with vertices
+V: every input point is inside by construction.  get_mesh's default `mesh_bound_mask=None` applies no
+hull mask (eval_points already returns 100 outside the scene bound).
 The vertex normals the reference takes from open3d (`compute_vertex_normals`, open3d is not in
 this image) are restated by `vertex_normals` on the device: area-weighted sums of the unnormalised triangle normals, normalised, with (0,0,1) for a
 vertex whose sum vanishes (open3d TriangleMesh::ComputeVertexNormals + MeshBase::NormalizeNormals).
@@ -37,6 +46,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import bound as _bound
 
 
 def get_grid_uniform(bound, resolution, padding=0.05):
@@ -182,6 +192,155 @@ def point_masks(points, keyframe_dict, estimate_c2w_list, idx, H, W, fx, fy, cx,
     return seen, fore, ~(seen | fore)
 
 
+# ---- the mesh bound from the keyframes (csrc/bound.hip, pnr/bound.py) -----------------------------
+
+DEPTH_TRUNC = 1000.0   # src/utils/Mesher.py:261 (open3d's depth_trunc)
+
+
+class FramePoints(object):
+    """The point set P of the mesh bound on the device (include/pnr.h `pnr_bound_frames`): the valid
+    depth pixels (finite, 0 < d <= depth_trunc) of the `stride` lattice of every keyframe, back-projected
+    as the map growth does (index k H W + v W + u), then `extra` (n,3) points (index K H W + e).
+    depth (K,H,W) and c2w (K,4,4) are float32 device tensors."""
+
+    def __init__(self, depth, c2w, fx, fy, cx, cy, stride=1, depth_trunc=DEPTH_TRUNC, extra=None):
+        self.lib = _lib.load()
+        self.depth = depth.detach().float().contiguous()
+        self.c2w = c2w.detach().to(self.depth.device).float().contiguous()
+        _lib.require_cuda(self.depth, self.c2w)
+        if self.depth.dim() != 3 or self.c2w.shape != (self.depth.shape[0], 4, 4):
+            raise ValueError('pnr.mesher: depth (K,H,W) and c2w (K,4,4) expected')
+        self.device = self.depth.device
+        self.extra = None
+        if extra is not None and len(extra):
+            self.extra = torch.as_tensor(extra).detach().to(self.device).float().reshape(-1, 3).contiguous()
+        K, H, W = self.depth.shape
+        f = _lib.BoundFrames()
+        f.depth, f.c2w = self.depth.data_ptr() if K else None, self.c2w.data_ptr() if K else None
+        f.K, f.H, f.W, f.stride = K, H, W, int(stride)
+        f.fx, f.fy, f.cx, f.cy, f.depth_trunc = float(fx), float(fy), float(cx), float(cy), float(depth_trunc)
+        f.extra_xyz = self.extra.data_ptr() if self.extra is not None else None
+        f.n_extra = self.extra.shape[0] if self.extra is not None else 0
+        self.frames = f
+        self.n_index = K * H * W + f.n_extra
+        self.max_dirs = int(self.lib.pnr_bound_support_max_dirs())
+        self.support_launches = 0
+
+    def support(self, dirs):
+        """pnr_bound_support: (h float32 (D,), arg int64 (D,)) device tensors for `dirs` (D,3); h = -inf
+        and arg = -1 when no point is valid.  More directions than the library's cap are split."""
+        d = torch.as_tensor(dirs).detach().to(self.device).float().reshape(-1, 3).contiguous()
+        D = d.shape[0]
+        h = torch.empty(D, dtype=torch.float32, device=self.device)
+        arg = torch.empty(D, dtype=torch.int64, device=self.device)
+        st = _lib.stream_of(self.device)
+        for s in range(0, D, self.max_dirs):
+            n = min(self.max_dirs, D - s)
+            nbytes = self.lib.pnr_bound_support_workspace_bytes(ctypes.byref(self.frames), n)
+            if nbytes == 0:
+                raise RuntimeError('pnr: bound_support failed (bad argument)')
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.pnr_bound_support(ctypes.byref(self.frames), _lib.ptr(d[s:s + n]), n,
+                                                  _lib.ptr(h[s:s + n]), _lib.ptr(arg[s:s + n]), _lib.ptr(ws), nbytes,
+                                                  st), 'bound_support')
+            self.support_launches += 1
+        return h, arg
+
+    def points(self, idx):
+        """pnr_bound_points: float32 (n,3) positions of the indices `idx`; NaN rows for indices that
+        name no valid point."""
+        i = torch.as_tensor(idx).detach().to(self.device).long().reshape(-1).contiguous()
+        xyz = torch.empty((i.shape[0], 3), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pnr_bound_points(ctypes.byref(self.frames), _lib.ptr(i), i.shape[0], _lib.ptr(xyz),
+                                             _lib.stream_of(self.device)), 'bound_points')
+        return xyz
+
+    # the two callables of pnr.bound.build_hull: one small host read each
+    def support_np(self, dirs):
+        h, arg = self.support(torch.from_numpy(np.ascontiguousarray(dirs, dtype=np.float32)))
+        return h.cpu().numpy(), arg.cpu().numpy()
+
+    def points_np(self, idx):
+        return self.points(torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64))).cpu().numpy()
+
+
+def bound_contains(points, planes, chunk=1 << 22):
+    """pnr_bound_contains_*: bool (P,) device tensor, True where (x a + y b) + z c <= d holds in unfused
+    float64 for every row (a, b, c, d) of the device tensor `planes` (F,4) float64.  `points` (P,3):
+    a float32 or float64 tensor (moved to the planes' device) or numpy array; any other dtype is taken
+    as float64.  Runs in chunks of `chunk` points."""
+    lib = _lib.load()
+    _lib.require_cuda(planes)
+    pl = planes.detach().double().reshape(-1, 4).contiguous()
+    p = points if isinstance(points, torch.Tensor) else torch.from_numpy(np.asarray(points))
+    p = p.detach().to(pl.device)
+    if p.dtype != torch.float32:
+        p = p.double()
+    p = p.reshape(-1, 3).contiguous()
+    fn = lib.pnr_bound_contains_f32 if p.dtype == torch.float32 else lib.pnr_bound_contains_f64
+    out = torch.empty(p.shape[0], dtype=torch.uint8, device=pl.device)
+    st = _lib.stream_of(pl.device)
+    for s in range(0, p.shape[0], chunk):
+        n = min(chunk, p.shape[0] - s)
+        _lib.check(fn(_lib.ptr(p[s:s + n]), n, _lib.ptr(pl) if pl.shape[0] else None, pl.shape[0],
+                      _lib.ptr(out[s:s + n]), st), 'bound_contains')
+    return out.bool()
+
+
+class FrameBound(object):
+    """The mesh bound of src/utils/Mesher.py:214-279: the convex hull (to the tolerance `eps`, see
+    pnr/bound.py) of the keyframes' back-projected depth pixels and camera centres, scaled by
+    `bound_scale` about its centre (:273).
+
+    planes           (F,4) float64 on the device: a point is inside when n.p <= off for every row
+    planes_unscaled  the same before the scaling (host, float64)
+    vertices, faces  the hull's triangles (host; vertices (V,3) float64 unscaled, rows of the point set)
+    vertex_index     (V,) their indices in the point set
+    center           (3,) the mean of the vertices (open3d's get_center() of the hull mesh)
+    stats            rounds, directions, support_calls, facets, vertices of the build
+    `contains(points)` is the reference's `mesh_bound.contains`; the object is callable, so it is a valid
+    `mesh_bound_mask` of Mesher.get_mesh."""
+
+    def __init__(self, hull, bound_scale, eps, device):
+        self.device = torch.device(device)
+        self.eps = float(eps)
+        self.bound_scale = float(bound_scale)
+        self.planes_unscaled = hull.planes
+        self.planes_host = _bound.scale_planes(hull.planes, hull.center, bound_scale)
+        self.planes = torch.from_numpy(self.planes_host).to(self.device)
+        self.vertices, self.faces, self.vertex_index = hull.vertices, hull.faces, hull.vertex_index
+        self.center = hull.center
+        self.capped = hull.capped
+        self.stats = dict(hull.stats)
+
+    def contains(self, points, chunk=1 << 22):
+        return bound_contains(points, self.planes, chunk)
+
+    __call__ = contains
+
+
+def get_bound_from_frames(keyframe_dict, H, W, fx, fy, cx, cy, scale=1.0, bound_scale=1.02, device='cuda:0',
+                          stride=1, eps=None, max_facets=16384):
+    """src/utils/Mesher.py:214-279 on the device: the FrameBound of the keyframes' 'depth' (H,W) and
+    'est_c2w' (4,4).  `eps` defaults to the reference's TSDF voxel 4 scale / 512; `stride` >= 1 thins the
+    pixels to a lattice.  One small host read per refinement round, as marching cubes reads its counts."""
+    if len(keyframe_dict) == 0:
+        raise ValueError('pnr.mesher: get_bound_from_frames needs at least one keyframe')
+    device = torch.device(device)
+    depth = torch.stack([kf['depth'].to(device).reshape(H, W) for kf in keyframe_dict]).float()
+    c2w = torch.stack([torch.as_tensor(kf['est_c2w']).detach().to(device).float().reshape(4, 4)
+                       for kf in keyframe_dict])
+    pts = FramePoints(depth, c2w, fx, fy, cx, cy, stride=stride, extra=c2w[:, :3, 3])
+    lattice = depth[:, ::stride, ::stride]
+    if not bool((torch.isfinite(lattice) & (lattice > 0) & (lattice <= DEPTH_TRUNC)).any()):
+        raise ValueError('pnr.mesher: get_bound_from_frames found no valid depth pixel')
+    eps =4.0 * float(scale) / 512.0 if eps is None else float(eps)
+    hull = _bound.build_hull(pts.support_np, pts.points_np, eps, max_facets)
+    fb = FrameBound(hull, bound_scale, eps, device)
+    fb.stats['support_launches'] = pts.support_launches
+    return fb
+
+
 def marching_cubes_volume(vol, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
     """Marching cubes over a float32 device tensor vol[ix, iy, iz] of any strides (no copy is made):
     vertices (V,3) float64 = origin + (i + t) spacing with t = (level - a) / (b - a) in float64, faces
@@ -324,8 +483,9 @@ class Mesher(object):
 
     cfg['meshing'] keys that are absent take the values of configs/pointNeRF_slam.yaml:29-38
     (MESHING_DEFAULTS); cfg['mapping']['marching_cubes_bound'] falls back to cfg['mapping']['bound'].
-    No dataset reader is built.  Out of scope: get_bound_from_frames (open3d's TSDF volume plus a
-    convex hull) -- see get_mesh's `mesh_bound_mask`."""
+    No dataset reader is built.  get_bound_from_frames returns a FrameBound (the hull of the depth
+    pixels to a tolerance, not of open3d's TSDF surface); get_mesh applies it with
+    `mesh_bound_mask='frames'`."""
 
     def __init__(self, cfg, args, slam, points_batch_size=500000, ray_batch_size=100000):
         self.points_batch_size = points_batch_size
@@ -364,6 +524,12 @@ class Mesher(object):
     def get_grid_uniform(self, resolution):
         return get_grid_uniform(self.marching_cubes_bound, resolution)
 
+    def get_bound_from_frames(self, keyframe_dict, scale=1, device='cuda:0', **kw):
+        """Mesher.get_bound_from_frames (:214-279): the FrameBound of the keyframes, scaled by
+        clean_mesh_bound_scale about its centre.  `kw`: stride, eps, max_facets."""
+        return get_bound_from_frames(keyframe_dict, self.H, self.W, self.fx, self.fy, self.cx, self.cy, scale=scale,
+                                     bound_scale=self.clean_mesh_bound_scale, device=device, **kw)
+
     def get_mesh(self, mesh_out_file, c, decoders, keyframe_dict, estimate_c2w_list, idx, device='cuda:0',
                  show_forecast=False, color=True, clean_mesh=True, get_mask_use_all_frames=False,
                  mesh_bound_mask=None):
@@ -371,13 +537,18 @@ class Mesher(object):
         returns (vertices (V,3) float64 divided by scale, faces (F,3) int32, colors (V,3) uint8 or None)
         on the device; None when the level set has no surface (the reference's except branch).
 
-        `mesh_bound_mask` stands in for the reference's convex hull (get_bound_from_frames, out of
-        scope): a bool tensor over the grid points, or a callable points (N,3) -> bool (N,).  With
-        show_forecast=False it sets the occupancy outside it to 100 (:433); with show_forecast=True
-        a callable also culls the faces whose vertices all lie outside it (:475-485).  Without it no
-        hull mask is applied."""
+        `mesh_bound_mask` is the reference's convex hull (get_bound_from_frames, :421 / :475):
+        'frames' builds the FrameBound of `keyframe_dict` at self.scale, as the reference does in every
+        extraction; a FrameBound or any callable points (N,3) -> bool (N,) is used as given; a bool
+        tensor over the grid points masks the grid alone.  With show_forecast=False it sets the occupancy
+        outside it to 100 (:433); with show_forecast=True a callable also culls the faces whose vertices
+        all lie outside it (:475-485).  None (the default) applies no hull mask."""
         with torch.no_grad():
             device = torch.device(device)
+            if isinstance(mesh_bound_mask, str):
+                if mesh_bound_mask != 'frames':
+                    raise ValueError(f"pnr.mesher: mesh_bound_mask {mesh_bound_mask!r} (the only name is 'frames')")
+                mesh_bound_mask = self.get_bound_from_frames(keyframe_dict, self.scale, device=device)
             grid = self.get_grid_uniform(self.resolution)
             points = grid['grid_points'].to(device)
             masks = dict(keyframe_dict=keyframe_dict, estimate_c2w_list=estimate_c2w_list, idx=idx, device=device,

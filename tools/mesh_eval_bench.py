@@ -16,6 +16,12 @@ fails or runs out of time no further child is started and the tool exits non-zer
 marching-cubes bytes are the traffic the algorithm needs: the volume read once (4 B/sample), the
 per-sample word written and read once (4 + 4 B), 24 B per vertex and 12 B per face written; the rate
 is those bytes over the time of the whole call (three launches and the host read of the counts).
+The `bound` step builds the mesh bound of the same keyframes (pnr.mesher.get_bound_from_frames) and
+writes profiles/mesh_bound.json: the whole hull build, its support launches alone (the build's own
+direction sets replayed without the host work between them), rounds / directions / facets, and
+`contains` over the grid -- each a wall time ending in a synchronise, the median of five.  The support
+pass is VALU work: 8 lane operations (5 arithmetic, one compare, two selects) per point and direction,
+reported against 78.6e12 lane operations/s (256 CUs x 4 SIMDs x 32 lanes per clock at 2.4 GHz).
 """
 import argparse
 import json
@@ -35,8 +41,61 @@ sys.path.insert(0, REPO)
 from bench import load_scene, FLOP_PER_POINT_FWD  # noqa: E402
 
 
-EXTRACT_STEPS = ('masks', 'mc', 'clean')
+EXTRACT_STEPS = ('masks', 'mc', 'clean', 'bound')
 HBM_BYTES_PER_S = 8e12
+VALU_LANE_OPS_PER_S = 256 * 4 * 32 * 2.4e9
+SUPPORT_LANE_OPS = 8    # per point and direction: 5 arithmetic, one compare, two selects
+
+
+def median_of(fn, n=5):
+    """(median seconds, last result) of fn() over `n` calls after one warm-up call; every call ends in
+    a device synchronise."""
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)), out
+
+
+def bound_step(m, keyframes, points, dev):
+    """The mesh bound of the keyframes: build, support launches alone, containment over the grid."""
+    import pnr
+    t_build, fb = median_of(lambda: m.get_bound_from_frames(keyframes, m.scale, device=dev))
+    depth = torch.stack([kf['depth'] for kf in keyframes]).float()
+    c2w = torch.stack([kf['est_c2w'] for kf in keyframes]).to(dev).float()
+    fp = pnr.mesher.FramePoints(depth, c2w, m.fx, m.fy, m.cx, m.cy, extra=c2w[:, :3, 3])
+    calls = []
+
+    def recording(dirs):
+        calls.append(torch.from_numpy(np.ascontiguousarray(dirs, dtype=np.float32)).to(dev))
+        return fp.support_np(dirs)
+
+    hull = pnr.bound.build_hull(recording, fp.points_np, fb.eps)
+    assert np.array_equal(hull.faces, fb.faces)
+
+    def replay():
+        for d in calls:
+            fp.support(d)
+
+    launches0 = fp.support_launches
+    t_support, _ = median_of(replay)
+    launches = (fp.support_launches - launches0) // 6
+    t_contains, inside = median_of(lambda: fb.contains(points))
+    slots = depth.numel() + c2w.shape[0]
+    dirs = sum(int(d.shape[0]) for d in calls)
+    lane_ops = SUPPORT_LANE_OPS * slots * dirs
+    return {'build_ms': round(t_build * 1e3, 3), 'support_ms': round(t_support * 1e3, 3),
+            'support_calls': len(calls), 'support_launches': launches, 'rounds': fb.stats['rounds'],
+            'directions': dirs, 'facets': fb.stats['facets'], 'hull_vertices': fb.stats['vertices'],
+            'capped': bool(fb.capped), 'eps': fb.eps, 'point_slots': slots,
+            'support_lane_ops': lane_ops, 'support_lane_ops_per_s': float(f'{lane_ops / t_support:.4g}'),
+            'share_of_valu_rate': float(f'{lane_ops / t_support / VALU_LANE_OPS_PER_S:.3g}'),
+            'contains_ms': round(t_contains * 1e3, 3), 'contains_points': int(points.shape[0]),
+            'contains_inside': int(inside.sum())}
 
 
 def timed(fn, iters):
@@ -87,6 +146,8 @@ def extract_step(step, args):
                                             args.iters)
             out[name] = {'ms': round(t * 1e3, 3), 'seen': int(seen.sum()), 'forecast': int(fore.sum()),
                          'unseen': int(unseen.sum())}
+    elif step == 'bound':
+        out.update(bound_step(m, keyframes, points, dev))
     else:
         z = m.eval_points(points, dec, None, 'fine', dev)[:, -1].contiguous()
         t, (v, f) = timed(lambda: pnr.mesher.marching_cubes(z, grid['xyz'], m.level_set), args.iters)
@@ -176,6 +237,15 @@ def main():
         del out, gd
         torch.cuda.empty_cache()
         res['extract'] = run_extract(args)
+        b = res['extract']['bound']
+        print(f"bound: hull build {b['build_ms']} ms (support launches alone {b['support_ms']} ms, {b['rounds']} rounds, "
+              f"{b['directions']} directions, {b['facets']} facets), contains over the grid {b['contains_ms']} ms; "
+              f"the grid query of this run {res['ms']} ms")
+        os.makedirs(os.path.join(REPO, 'profiles'), exist_ok=True)
+        with open(os.path.join(REPO, 'profiles', 'mesh_bound.json'), 'w') as fh:
+            json.dump({'resolution': R, 'keyframes': args.keyframes, 'frame': [680, 1200], 'timing':
+                       'wall time ending in a synchronise, median of five', 'grid_query_ms': res['ms'], **b}, fh, indent=1)
+            fh.write('\n')
     print(json.dumps(res))
 
 
