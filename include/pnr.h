@@ -603,6 +603,29 @@ int pnr_bound_contains_f32(const float* p, int64_t P, const double* planes, int3
 int pnr_bound_contains_f64(const double* p, int64_t P, const double* planes, int32_t F, uint8_t* inside,
                            void* stream);
 
+/* ---- two-way descriptor matching (src/Tracker.py:398-440, nn_match_two_way; additions to ABI 14) ----
+ * desc1 (D,N), desc2 (D,M): float32 row-major with unit-norm columns (the reference's SuperPoint layout);
+ * D a multiple of 32 in [32, 512], N, M <= 2^20.  dot = desc1^T desc2 on v_mfma_f32_32x32x2_f32 (each
+ * element one fp32 fma chain in ascending k), clipped to [-1, 1]; per row i the column j* of the largest
+ * dot and per column the row of the largest dot, the lowest index among bitwise-equal dots (np.argmin's
+ * first occurrence on the distance).  Row i is kept when score = sqrtf(2 - 2 dot[i][j*]) < nn_thresh and
+ * column j* chose row i.  The L kept rows are written in ascending i: idx1[0..L) = i, idx2[0..L) = j*
+ * (int32), score[0..L) (float32), *count = L (int32); idx1, idx2, score hold N elements, of which the
+ * call writes the first L only.  N = 0 or M = 0: *count = 0.  The N x M product never reaches memory, and
+ * equal arguments give equal bits (integer atomics only).  Non-finite descriptors are the caller's error
+ * (a NaN dot counts as -1).
+ * workspace: pnr_match_workspace_bytes(N, M) bytes (0 for sizes the call refuses), 8-byte aligned, any
+ * contents.  After the call it holds uint64 row_key[N] then col_key[M]:
+ *   key = u << 32 | (0xFFFFFFFF - index of the best partner)
+ *   u   = the dot's float32 bits b mapped monotonically: b | 0x80000000 for b >= 0, ~b for a negative dot
+ * so a caller can read every row's nearest column, kept or not.
+ * D unsupported, nn_thresh negative or NaN, a size out of range, a null pointer: PNR_E_ARG; a short
+ * workspace: PNR_E_WORKSPACE; nothing is launched. */
+size_t pnr_match_workspace_bytes(int64_t N, int64_t M);
+int pnr_match_two_way(const float* desc1, const float* desc2, int32_t D, int64_t N, int64_t M, float nn_thresh,
+                      int32_t* idx1, int32_t* idx2, float* score, int32_t* count, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* ---- diagnostics (not on the reference API) ----------------------------------------------- */
 /* Kernel timing: while enabled, every launch of the timed kernels is bracketed by hipEvents on
  * its own stream.  pnr_timing_read synchronises those events and returns, for `kernel`

@@ -92,6 +92,9 @@ int launch_bound_support(const pnr_bound_frames&, const float*, int32_t, float*,
 int launch_bound_points(const pnr_bound_frames&, const int64_t*, int64_t, float*, hipStream_t);
 int launch_bound_contains_f32(const float*, int64_t, const double*, int32_t, uint8_t*, hipStream_t);
 int launch_bound_contains_f64(const double*, int64_t, const double*, int32_t, uint8_t*, hipStream_t);
+size_t match_workspace_bytes(int64_t, int64_t);
+int launch_match_two_way(const float*, const float*, int32_t, int64_t, int64_t, float, int32_t*, int32_t*, float*,
+                         int32_t*, void*, size_t, hipStream_t);
 
 }  // namespace pnr
 
@@ -1623,6 +1626,16 @@ int pnr_bound_contains_f32(const float* p, int64_t P, const double* planes, int3
 int pnr_bound_contains_f64(const double* p, int64_t P, const double* planes, int32_t F, uint8_t* inside,
                            void* stream) {
   return launch_bound_contains_f64(p, P, planes, F, inside, (hipStream_t)stream);
+}
+
+// ---- two-way descriptor matching (match.hip; Tracker.py:398-440) --------------------------------------
+size_t pnr_match_workspace_bytes(int64_t N, int64_t M) { return match_workspace_bytes(N, M); }
+
+int pnr_match_two_way(const float* desc1, const float* desc2, int32_t D, int64_t N, int64_t M, float nn_thresh,
+                      int32_t* idx1, int32_t* idx2, float* score, int32_t* count, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+  return launch_match_two_way(desc1, desc2, D, N, M, nn_thresh, idx1, idx2, score, count, workspace, workspace_bytes,
+                              (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -10,6 +10,8 @@ from .points import NeuralPoints
 from .renderer import Renderer, get_rays, get_rays_from_uv, get_samples
 from .common import scaled_bound, get_camera_from_tensor, get_tensor_from_camera, quad2rotation, random_select
 from .tracking import TrackStep, track_frame
+from . import matching
+from .matching import match_two_way, nn_match_two_way
 from .mapping import BundleAdjust, MapGraph, MapStep, WindowSampler
 from . import mesher, logger
 from .logger import Logger, load_ckpt
@@ -18,7 +20,8 @@ from .mesher import Mesher
 __all__ = ['Renderer', 'MLP', 'PARAM_ORDER', 'FC_ORDER', 'NeuralPoints', 'get_model', 'load_config', 'ROOM0_CFG', 'get_rays',
            'get_rays_from_uv', 'scaled_bound', 'get_camera_from_tensor', 'get_tensor_from_camera',
            'quad2rotation', 'TrackStep', 'track_frame', 'get_samples', 'random_select', 'mesher', 'logger', 'Logger',
-           'load_ckpt', 'Mesher', 'BundleAdjust', 'MapGraph', 'MapStep', 'WindowSampler']
+           'load_ckpt', 'Mesher', 'BundleAdjust', 'MapGraph', 'MapStep', 'WindowSampler', 'matching', 'match_two_way',
+           'nn_match_two_way']
 
 
 def library():

@@ -227,6 +227,9 @@ _SIGS = {
     'pnr_bound_points': (ctypes.c_int, [PBoundFrames, c_void_p, c_int64, c_void_p, c_void_p]),
     'pnr_bound_contains_f32': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
     'pnr_bound_contains_f64': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
+    'pnr_match_workspace_bytes': (c_size_t, [c_int64, c_int64]),
+    'pnr_match_two_way': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int64, c_float, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'pnr_timing_enable': (ctypes.c_int, [ctypes.c_int]),
     'pnr_timing_read': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_int64), ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(c_int64)]),
