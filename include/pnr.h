@@ -626,6 +626,58 @@ int pnr_match_two_way(const float* desc1, const float* desc2, int32_t D, int64_t
                       int32_t* idx1, int32_t* idx2, float* score, int32_t* count, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---- SuperPoint on the device (src/demo_superpoint.py:78-293; additions to ABI 14) --------------------
+ * One convolution layer of the network: x (Cin,H,W) -> out, float32 planar, batch 1, stride 1, ksize 3 with
+ * zero padding 1 or ksize 1.  Cin in {1, 64, 128, 256}, Cout in {64, 128, 256, 65}; Cin = 1 is served for
+ * ksize 3 with NONE / RELU only.  H, W > 0 need no alignment.
+ *   w_packed  [ksize^2][Cin][cout_pad] float32, cout_pad = Cout rounded up to a multiple of 64 and the padding
+ *             zero: w_packed[ky ksize + kx][ci][co] = conv.weight[co][ci][ky][kx]; 16-byte aligned
+ *   bias      [Cout]
+ * Arithmetic: v_mfma_f32_32x32x2_f32 (Cin = 1: fmaf).  Every output is one fp32 chain formed by one wave:
+ * acc = bias, then cin chunks ascending (8 channels for ksize 3, 16 for ksize 1), inside a chunk the taps
+ * ascending (ky major), inside a tap the cin pairs ascending; Cin = 1: bias, then the 9 taps ascending.  A
+ * pixel outside the image contributes 0.  Equal arguments give equal bits; every output element is written.
+ * Epilogues:
+ *   NONE             out (Cout,H,W) = the chain
+ *   RELU             out (Cout,H,W) = max(chain, 0)
+ *   RELU_POOL2       out (Cout,H/2,W/2) = 2 x 2 / stride 2 max of the RELU output; H and W even
+ *   SOFTMAX_HEATMAP  Cout = 65, ksize 1: out (65,H,W) = the chain (bitwise NONE's), and
+ *                    heat[8 y + (c >> 3)][8 x + (c & 7)] = expf(out[c][y][x]) / (sum over the 65 channels of
+ *                    expf(out[.][y][x]) + 1e-5f) for c < 64 into heat (8 H, 8 W); no maximum is subtracted
+ *                    (demo_superpoint.py:248-258 as it stands)
+ *   L2NORM           Cout = 256, ksize 1: out (256,H,W) = chain / sqrtf(sum over the 256 channels of chain^2)
+ * heat is read by SOFTMAX_HEATMAP only.  Anything else, a null pointer, or a tensor of 2^31 elements or
+ * more: PNR_E_ARG, nothing is launched. */
+typedef enum pnr_conv_epilogue {
+  PNR_CONV_NONE = 0,
+  PNR_CONV_RELU = 1,
+  PNR_CONV_RELU_POOL2 = 2,
+  PNR_CONV_SOFTMAX_HEATMAP = 3,
+  PNR_CONV_L2NORM = 4
+} pnr_conv_epilogue;
+int pnr_conv2d_fwd(const float* x, const float* w_packed, const float* bias, float* out, float* heat, int32_t Cin,
+                   int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t epilogue, void* stream);
+/* Keypoints of a heatmap (H,W) float32, H and W positive multiples of 8, H W < 2^28 (demo_superpoint.py:158-275).
+ * Candidates: heat >= conf_thresh (conf_thresh > 0).  Candidate p = y W + x ranks above q when heat[p] >
+ * heat[q], or they are equal and p < q.  Greedy NMS in that order: a candidate not yet suppressed is kept and
+ * suppresses every candidate at Chebyshev distance <= nms_dist (0 <= nms_dist <= 64).  Then kept points with
+ * x < border, x >= W - border, y < border or y >= H - border are dropped.  The result does not depend on
+ * scheduling (a fixed point whose decisions are final; csrc/keypoints.hip).
+ * workspace: pnr_superpoint_workspace_bytes(H, W) bytes (0 for sizes the call refuses), 8-byte aligned, any
+ * contents.  After the call it holds int32 count at byte 0 and, from byte 64, `count` uint64 keys in no
+ * particular order:  key = heat bits << 32 | (0xFFFFFFFF - p).  Sorted descending they are the reference's
+ * output order (confidence descending; ties, which numpy leaves to an unstable sort, by ascending p).
+ * Bad arguments: PNR_E_ARG; a short workspace: PNR_E_WORKSPACE; nothing is launched. */
+size_t pnr_superpoint_workspace_bytes(int32_t H, int32_t W);
+int pnr_superpoint_keypoints(const float* heat, int32_t H, int32_t W, float conf_thresh, int32_t nms_dist,
+                             int32_t border, void* workspace, size_t workspace_bytes, void* stream);
+/* Descriptors of N keypoints (demo_superpoint.py:277-292): pts (3,N) float32 rows x, y, confidence in pixels
+ * of the full image; coarse (256,Hc,Wc) the L2NORM output.  desc (256,N) float32: the bilinear sample of
+ * coarse at (x / 8 - 0.5, y / 8 - 0.5) with zeros outside (grid_sample, align_corners = False), divided by
+ * its Euclidean norm -- the layout pnr_match_two_way takes.  N = 0 launches nothing. */
+int pnr_superpoint_sample_desc(const float* coarse, int32_t Hc, int32_t Wc, const float* pts, int64_t N, float* desc,
+                               void* stream);
+
 /* ---- diagnostics (not on the reference API) ----------------------------------------------- */
 /* Kernel timing: while enabled, every launch of the timed kernels is bracketed by hipEvents on
  * its own stream.  pnr_timing_read synchronises those events and returns, for `kernel`

@@ -95,6 +95,11 @@ int launch_bound_contains_f64(const double*, int64_t, const double*, int32_t, ui
 size_t match_workspace_bytes(int64_t, int64_t);
 int launch_match_two_way(const float*, const float*, int32_t, int64_t, int64_t, float, int32_t*, int32_t*, float*,
                          int32_t*, void*, size_t, hipStream_t);
+int launch_conv2d(const float*, const float*, const float*, float*, float*, int32_t, int32_t, int32_t, int32_t,
+                  int32_t, int32_t, hipStream_t);
+size_t superpoint_workspace_bytes(int32_t, int32_t);
+int launch_superpoint_keypoints(const float*, int32_t, int32_t, float, int32_t, int32_t, void*, size_t, hipStream_t);
+int launch_superpoint_sample_desc(const float*, int32_t, int32_t, const float*, int64_t, float*, hipStream_t);
 
 }  // namespace pnr
 
@@ -1636,6 +1641,25 @@ int pnr_match_two_way(const float* desc1, const float* desc2, int32_t D, int64_t
                       size_t workspace_bytes, void* stream) {
   return launch_match_two_way(desc1, desc2, D, N, M, nn_thresh, idx1, idx2, score, count, workspace, workspace_bytes,
                               (hipStream_t)stream);
+}
+
+// ---- SuperPoint (conv.hip, keypoints.hip; demo_superpoint.py:78-293) ----------------------------------
+int pnr_conv2d_fwd(const float* x, const float* w_packed, const float* bias, float* out, float* heat, int32_t Cin,
+                   int32_t Cout, int32_t H, int32_t W, int32_t ksize, int32_t epilogue, void* stream) {
+  return launch_conv2d(x, w_packed, bias, out, heat, Cin, Cout, H, W, ksize, epilogue, (hipStream_t)stream);
+}
+
+size_t pnr_superpoint_workspace_bytes(int32_t H, int32_t W) { return superpoint_workspace_bytes(H, W); }
+
+int pnr_superpoint_keypoints(const float* heat, int32_t H, int32_t W, float conf_thresh, int32_t nms_dist,
+                             int32_t border, void* workspace, size_t workspace_bytes, void* stream) {
+  return launch_superpoint_keypoints(heat, H, W, conf_thresh, nms_dist, border, workspace, workspace_bytes,
+                                     (hipStream_t)stream);
+}
+
+int pnr_superpoint_sample_desc(const float* coarse, int32_t Hc, int32_t Wc, const float* pts, int64_t N, float* desc,
+                               void* stream) {
+  return launch_superpoint_sample_desc(coarse, Hc, Wc, pts, N, desc, (hipStream_t)stream);
 }
 
 }  // extern "C"

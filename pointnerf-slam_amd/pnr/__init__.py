@@ -12,6 +12,8 @@ from .common import scaled_bound, get_camera_from_tensor, get_tensor_from_camera
 from .tracking import TrackStep, track_frame
 from . import matching
 from .matching import match_two_way, nn_match_two_way
+from . import superpoint
+from .superpoint import SuperPointNet, SuperPointFrontend
 from .mapping import BundleAdjust, MapGraph, MapStep, WindowSampler
 from . import mesher, logger
 from .logger import Logger, load_ckpt
@@ -21,7 +23,7 @@ __all__ = ['Renderer', 'MLP', 'PARAM_ORDER', 'FC_ORDER', 'NeuralPoints', 'get_mo
            'get_rays_from_uv', 'scaled_bound', 'get_camera_from_tensor', 'get_tensor_from_camera',
            'quad2rotation', 'TrackStep', 'track_frame', 'get_samples', 'random_select', 'mesher', 'logger', 'Logger',
            'load_ckpt', 'Mesher', 'BundleAdjust', 'MapGraph', 'MapStep', 'WindowSampler', 'matching', 'match_two_way',
-           'nn_match_two_way']
+           'nn_match_two_way', 'superpoint', 'SuperPointNet', 'SuperPointFrontend']
 
 
 def library():

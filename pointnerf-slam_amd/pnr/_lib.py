@@ -230,6 +230,12 @@ _SIGS = {
     'pnr_match_workspace_bytes': (c_size_t, [c_int64, c_int64]),
     'pnr_match_two_way': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int64, c_float, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'pnr_conv2d_fwd': (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                      c_int32, c_int32, c_int32, c_void_p]),
+    'pnr_superpoint_workspace_bytes': (c_size_t, [c_int32, c_int32]),
+    'pnr_superpoint_keypoints': (ctypes.c_int, [c_void_p, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p,
+                                                c_size_t, c_void_p]),
+    'pnr_superpoint_sample_desc': (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     'pnr_timing_enable': (ctypes.c_int, [ctypes.c_int]),
     'pnr_timing_read': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_int64), ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(c_int64)]),
