@@ -678,6 +678,57 @@ int pnr_superpoint_keypoints(const float* heat, int32_t H, int32_t W, float conf
 int pnr_superpoint_sample_desc(const float* coarse, int32_t Hc, int32_t Wc, const float* pts, int64_t N, float* desc,
                                void* stream);
 
+/* ---- relative pose from matches (src/Tracker.py:356-360 estimatePose, :458-610; additions to ABI 14) ----
+ * All float64.  x1, x2: (L,2) normalised image coordinates of the matches in the first and the second view
+ * (cv2.findEssentialMat's points1, points2: x2^T E x1 = 0); 5 <= L <= 2^20, 1 <= S <= 2^16 samples.
+ * The draw.  Sample s takes 5 distinct match indices: draw d = 0..4 tries retry = 0, 1, ...
+ *   z = (seed << 32 | s) * 0x9E3779B97F4A7C15 + (d << 32 | retry) * 0xD1B54A32D192ED03        (mod 2^64)
+ *   z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^= z >> 31
+ *   index = ((z >> 32) * L) >> 32
+ * and keeps the first index that differs from the draws before it; after 64 refusals it walks index + 1
+ * (mod L) instead.  The draws depend on (seed, s, L) alone, not on the launch.
+ * The solver (Nister's five-point method) gives sample s up to 10 essential matrices, unit Frobenius norm,
+ * at hypotheses 10 s + r in ascending order of the root z of the degree-10 polynomial; unused slots and
+ * rank-deficient samples are flagged invalid and hold zeros.
+ * Scoring.  err = (x2^T E x1)^2 / (a0^2 + a1^2 + b0^2 + b1^2), a = E x1, b = E^T x2 (cv2's Sampson error); a
+ * match is an inlier when err <= threshold^2.  The best hypothesis has the most inliers, the lowest index
+ * among equal counts: equal arguments give equal bits.
+ * pose (37): E (9) | R (9) | t (3) | Trc (16), row-major, x2 ~ R x1 + t, Trc = [R t; 0 1].  R, t: E = U diag V^T
+ * by one-sided Jacobi, R1 = U W V^T, R2 = U W^T V^T (determinants +1), t = +-u3; the inliers are triangulated
+ * under (R1,t), (R2,t), (R1,-t), (R2,-t) and the first candidate with the most points of depth in (0, 50) in
+ * both views wins (cv2.recoverPose).  mask (L) uint8 and *count: the inliers of E, from a plain float64
+ * evaluation.  No valid hypothesis: count 0, mask 0, E = 0, R = I, t = 0.
+ * workspace: pnr_relpose_workspace_bytes(L, S) bytes (0 for sizes the call refuses), 8-byte aligned, any
+ * contents.  After the call: uint64 best key = count << 32 | (0xFFFFFFFF - hypothesis) at byte 0 (0: none);
+ * from byte 64 the candidates (10 S, 9) float64; then the samples (S,5) int32 (rounded up to 8 bytes); then
+ * valid (10 S) uint8.
+ * A size out of range, a negative or NaN threshold, a null pointer: PNR_E_ARG; a short workspace:
+ * PNR_E_WORKSPACE; nothing is launched. */
+size_t pnr_relpose_workspace_bytes(int64_t L, int64_t S);
+int pnr_relpose_estimate(const double* x1, const double* x2, int64_t L, int64_t S, uint32_t seed, double threshold,
+                         double* pose, uint8_t* mask, int32_t* count, void* workspace, size_t workspace_bytes,
+                         void* stream);
+/* The solver alone: x1, x2 (S,5,2) -> E (S,10,9), valid (S,10) as above.  0 <= S <= 2^16. */
+int pnr_fivept_solve(const double* x1, const double* x2, int64_t S, double* E, uint8_t* valid, void* stream);
+/* DLT triangulation (src/utils/utils_geom.py:140-207).  Tcw_1, Tcw_2: (4,4) row-major world-to-camera poses;
+ * kpn_1, kpn_2: (L,2) normalised keypoints.  Per match the rows x P[2] - P[0], y P[2] - P[1] of both views
+ * form A (4,4); X is its right singular vector of the smallest singular value by one-sided Jacobi on A;
+ * pts3d (L,3) = X[:3] / X[3], good (L) uint8 = X[3] != 0.  With K (3,3) not null also, per view, q = K (Rcw p +
+ * tcw): uv (L,2) = q[:2] / q[2] and z (L) = q[2] (src/camera.py:62-68).  L = 0 launches nothing. */
+int pnr_triangulate(const double* Tcw_1, const double* Tcw_2, const double* kpn_1, const double* kpn_2, int64_t L,
+                    const double* K, double* pts3d, uint8_t* good, double* uv1, double* z1, double* uv2, double* z2,
+                    void* stream);
+/* The pseudo-depth map (Tracker.py:571-610).  uv (n,2) float64 pixels (u column, v row), depth (n) float64,
+ * out (H,W) float32.  Background 0.  Point i paints rows [int(v - patch), int(v + patch)) x columns
+ * [int(u - patch), int(u + patch)) when patch < v < H - patch and patch < u < W - patch, else the pixel
+ * (int(v), int(u)) when 0 < v < H and 0 < u < W; a pixel painted more than once keeps the highest i.
+ * workspace: pnr_paint_depth_workspace_bytes(H, W) = 4 H W bytes (0 when H W >= 2^30 or a side < 1), 4-byte
+ * aligned, any contents.  Deviations from the reference: it pairs every coordinate with every depth (each
+ * patch ends with the last depth), compares u with H, and fills the background with rand / 10000. */
+size_t pnr_paint_depth_workspace_bytes(int32_t H, int32_t W);
+int pnr_paint_depth(const double* uv, const double* depth, int64_t n, int32_t H, int32_t W, int32_t patch, float* out,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- diagnostics (not on the reference API) ----------------------------------------------- */
 /* Kernel timing: while enabled, every launch of the timed kernels is bracketed by hipEvents on
  * its own stream.  pnr_timing_read synchronises those events and returns, for `kernel`

@@ -100,6 +100,15 @@ int launch_conv2d(const float*, const float*, const float*, float*, float*, int3
 size_t superpoint_workspace_bytes(int32_t, int32_t);
 int launch_superpoint_keypoints(const float*, int32_t, int32_t, float, int32_t, int32_t, void*, size_t, hipStream_t);
 int launch_superpoint_sample_desc(const float*, int32_t, int32_t, const float*, int64_t, float*, hipStream_t);
+size_t relpose_workspace_bytes(int64_t, int64_t);
+int launch_relpose_estimate(const double*, const double*, int64_t, int64_t, uint32_t, double, double*, uint8_t*,
+                            int32_t*, void*, size_t, hipStream_t);
+int launch_fivept_solve(const double*, const double*, int64_t, double*, uint8_t*, hipStream_t);
+int launch_triangulate(const double*, const double*, const double*, const double*, int64_t, const double*, double*,
+                       uint8_t*, double*, double*, double*, double*, hipStream_t);
+size_t paint_depth_workspace_bytes(int32_t, int32_t);
+int launch_paint_depth(const double*, const double*, int64_t, int32_t, int32_t, int32_t, float*, void*, size_t,
+                       hipStream_t);
 
 }  // namespace pnr
 
@@ -1641,6 +1650,33 @@ int pnr_match_two_way(const float* desc1, const float* desc2, int32_t D, int64_t
                       size_t workspace_bytes, void* stream) {
   return launch_match_two_way(desc1, desc2, D, N, M, nn_thresh, idx1, idx2, score, count, workspace, workspace_bytes,
                               (hipStream_t)stream);
+}
+
+// ---- relative pose (relpose.hip; Tracker.py:356-360, :458-610) ---------------------------------------------
+size_t pnr_relpose_workspace_bytes(int64_t L, int64_t S) { return relpose_workspace_bytes(L, S); }
+
+int pnr_relpose_estimate(const double* x1, const double* x2, int64_t L, int64_t S, uint32_t seed, double threshold,
+                         double* pose, uint8_t* mask, int32_t* count, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  return launch_relpose_estimate(x1, x2, L, S, seed, threshold, pose, mask, count, workspace, workspace_bytes,
+                                 (hipStream_t)stream);
+}
+
+int pnr_fivept_solve(const double* x1, const double* x2, int64_t S, double* E, uint8_t* valid, void* stream) {
+  return launch_fivept_solve(x1, x2, S, E, valid, (hipStream_t)stream);
+}
+
+int pnr_triangulate(const double* Tcw_1, const double* Tcw_2, const double* kpn_1, const double* kpn_2, int64_t L,
+                    const double* K, double* pts3d, uint8_t* good, double* uv1, double* z1, double* uv2, double* z2,
+                    void* stream) {
+  return launch_triangulate(Tcw_1, Tcw_2, kpn_1, kpn_2, L, K, pts3d, good, uv1, z1, uv2, z2, (hipStream_t)stream);
+}
+
+size_t pnr_paint_depth_workspace_bytes(int32_t H, int32_t W) { return paint_depth_workspace_bytes(H, W); }
+
+int pnr_paint_depth(const double* uv, const double* depth, int64_t n, int32_t H, int32_t W, int32_t patch, float* out,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+  return launch_paint_depth(uv, depth, n, H, W, patch, out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- SuperPoint (conv.hip, keypoints.hip; demo_superpoint.py:78-293) ----------------------------------

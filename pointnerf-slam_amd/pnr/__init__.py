@@ -14,6 +14,8 @@ from . import matching
 from .matching import match_two_way, nn_match_two_way
 from . import superpoint
 from .superpoint import SuperPointNet, SuperPointFrontend
+from . import relpose
+from .relpose import estimate_pose
 from .mapping import BundleAdjust, MapGraph, MapStep, WindowSampler
 from . import mesher, logger
 from .logger import Logger, load_ckpt
@@ -23,7 +25,8 @@ __all__ = ['Renderer', 'MLP', 'PARAM_ORDER', 'FC_ORDER', 'NeuralPoints', 'get_mo
            'get_rays_from_uv', 'scaled_bound', 'get_camera_from_tensor', 'get_tensor_from_camera',
            'quad2rotation', 'TrackStep', 'track_frame', 'get_samples', 'random_select', 'mesher', 'logger', 'Logger',
            'load_ckpt', 'Mesher', 'BundleAdjust', 'MapGraph', 'MapStep', 'WindowSampler', 'matching', 'match_two_way',
-           'nn_match_two_way', 'superpoint', 'SuperPointNet', 'SuperPointFrontend']
+           'nn_match_two_way', 'superpoint', 'SuperPointNet', 'SuperPointFrontend', 'relpose',
+           'estimate_pose']
 
 
 def library():

@@ -236,6 +236,15 @@ _SIGS = {
     'pnr_superpoint_keypoints': (ctypes.c_int, [c_void_p, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p,
                                                 c_size_t, c_void_p]),
     'pnr_superpoint_sample_desc': (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    'pnr_relpose_workspace_bytes': (c_size_t, [c_int64, c_int64]),
+    'pnr_relpose_estimate': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int64, ctypes.c_uint32, ctypes.c_double,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'pnr_fivept_solve': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'pnr_triangulate': (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'pnr_paint_depth_workspace_bytes': (c_size_t, [c_int32, c_int32]),
+    'pnr_paint_depth': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                       c_size_t, c_void_p]),
     'pnr_timing_enable': (ctypes.c_int, [ctypes.c_int]),
     'pnr_timing_read': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_int64), ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(c_int64)]),
