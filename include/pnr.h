@@ -603,6 +603,80 @@ int pnr_bound_contains_f32(const float* p, int64_t P, const double* planes, int3
 int pnr_bound_contains_f64(const double* p, int64_t P, const double* planes, int32_t F, uint8_t* inside,
                            void* stream);
 
+/* ---- block-sparse TSDF volume fused from keyframe depth (src/utils/Mesher.py:231-266: open3d's
+ * ScalableTSDFVolume.integrate per keyframe; additions to ABI 14) -----------------------------------
+ * Geometry.  Blocks of 16^3 voxels of edge voxel_length; block_length = 16 voxel_length.  A dense int32
+ * directory of dims[0] x dims[1] x dims[2] entries, entry index e = (bz dims[1] + by) dims[0] + bx, covers
+ * the box that starts at `origin`; it replaces open3d's unbounded hash, and surface outside it is dropped.
+ * Global voxel g_a = 16 b_a + i_a has its centre at X_a = origin_a + ((float)g_a + 0.5f) voxel_length
+ * (open3d's convention); voxel (i, j, k) of a block has voxel index (k 16 + j) 16 + i.  An entry >= 0 is the
+ * block's slot; a negative entry means no block (-1: dropped for want of a slot, INT32_MIN: never touched).
+ * `directory` holds pnr_tsdf_directory_bytes() bytes: int32 n_blocks, int32 dropped_blocks, padding to 256
+ * bytes, then the entries.  The slot arrays are the caller's, structure of arrays, max_blocks slots: tsdf
+ * and weight (max_blocks, 4096), rgb (max_blocks, 3, 4096), block_index (max_blocks) = the slot's entry
+ * index.  Rows at or above n_blocks are never read, so the arrays need no clearing.
+ * Required: 0 < sdf_trunc < block_length, fx, fy > 0, 1 <= max_blocks <= 2^17, dims >= 1 with a product
+ * <= 2^27, every pointer but rgb non-null (rgb NULL: no colour is kept).  All arithmetic is unfused float32.
+ *
+ * pnr_tsdf_integrate fuses K frames, depth (K,H,W), colour (K,H,W,3) or NULL, c2w (K,4,4), in call order:
+ *   valid depth   d finite and 0 < d <= depth_trunc.
+ *   allocate      for every valid pixel of frame k: p = rays_o + rays_d d on pnr_get_rays' float32 ray (the
+ *                 device function of pnr_points_add_frame / pnr_bound_frames); a non-finite p is skipped.
+ *                 Per axis the blocks floorf(((p_a - sdf_trunc) - origin_a) / block_length) ..
+ *                 floorf(((p_a + sdf_trunc) - origin_a) / block_length), clipped to the directory (open3d's
+ *                 touch rule: at most 8 blocks when 2 sdf_trunc <= block_length, 27 otherwise).  A touched
+ *                 entry without a block is born at the first frame k that touches it.  The new blocks take
+ *                 the slots after the existing ones in ascending entry index; those past max_blocks are
+ *                 dropped in that order, become -1 for good, and are counted once in dropped_blocks.  The
+ *                 call still returns 0.  No host read; the assignment depends on the arguments alone.
+ *   integrate     every block, for the frames k at or after its birth (a block that existed before the
+ *                 call: all K), every voxel, with R = c2w[:3,:3], t = c2w[:3,3], q = X - t:
+ *                   P_c = (R[0][c] q_0 + R[1][c] q_1) + R[2][c] q_2      (camera looks down -z, y up)
+ *                   zc = -P_2;                                           skip unless zc > 0
+ *                   uf = ((fx P_0) / zc + cx) + 0.5f, vf = ((-(fy P_1)) / zc + cy) + 0.5f
+ *                   u = floorf(uf), v = floorf(vf);                      skip unless 0 <= uf < W, 0 <= vf < H
+ *                   d = depth[k][v][u];                                  skip unless valid
+ *                   a = (u - cx) / fx, b = (v - cy) / fy, m = sqrtf((a a + b b) + 1)
+ *                   sdf = (d - zc) m;                                    skip if sdf <= -sdf_trunc
+ *                   s = fminf(1, sdf / sdf_trunc), w1 = w + 1
+ *                   tsdf = (tsdf w + s) / w1, rgb_c = (rgb_c w + colour[k][v][u][c]) / w1, w = w1
+ *                 (open3d's IntegrateWithDepthToCameraDistanceMultiplier as recalled; THIS statement is the
+ *                 contract).  So the volume depends on the sequence of frames alone, not on how calls
+ *                 batch them; only the slot order does.  A block is read once and written once per 64
+ *                 frames of a call; a conservative per-block frustum test skips frames that cannot reach
+ *                 the block and never changes a result.
+ * pnr_tsdf_extract_count / _emit give the zero crossings between neighbouring voxels: for every voxel of
+ * every block with w > 0 and each of its +x, +y, +z neighbours (axis a = 0, 1, 2; found through the directory
+ * when it lies in the next block, skipped when that block is absent) with w > 0, a point when tsdf0 and
+ * tsdf1 have strictly opposite signs (tsdf0 tsdf1 < 0):
+ *   s = tsdf0 / (tsdf0 - tsdf1);  xyz = X0, xyz_a = X0_a + voxel_length s;  rgb_c = rgb0_c + (rgb1_c - rgb0_c) s
+ * in order of (slot, voxel index, axis): equal arguments give equal bits.  _count writes the number of
+ * points to *n_points (device) and leaves the offsets in the workspace for _emit; xyz, rgb (n_points,3)
+ * float32, rgb may be NULL (and must be when the volume keeps no colour).
+ * ws: pnr_tsdf_workspace_bytes() bytes (0 for bad arguments), 4-byte aligned, any contents.  Bad arguments:
+ * PNR_E_ARG; a short workspace: PNR_E_WORKSPACE; nothing is launched. */
+typedef struct pnr_tsdf {
+  float origin[3];
+  float voxel_length, sdf_trunc, depth_trunc;
+  int32_t dims[3];      /* directory entries per axis                                          */
+  int32_t max_blocks;
+  int32_t H, W;
+  float fx, fy, cx, cy;
+  int32_t* directory;   /* pnr_tsdf_directory_bytes                                            */
+  float* tsdf;          /* (max_blocks, 4096)                                                  */
+  float* weight;        /* (max_blocks, 4096)                                                  */
+  float* rgb;           /* (max_blocks, 3, 4096) or NULL                                       */
+  int32_t* block_index; /* (max_blocks)                                                        */
+} pnr_tsdf;
+size_t pnr_tsdf_directory_bytes(const pnr_tsdf* vol);
+size_t pnr_tsdf_workspace_bytes(const pnr_tsdf* vol);
+/* Empties the volume: every entry INT32_MIN, both counters 0. */
+int pnr_tsdf_reset(const pnr_tsdf* vol, void* stream);
+int pnr_tsdf_integrate(const pnr_tsdf* vol, const float* depth, const float* color, const float* c2w, int32_t K,
+                       void* ws, size_t ws_bytes, void* stream);
+int pnr_tsdf_extract_count(const pnr_tsdf* vol, void* ws, size_t ws_bytes, int64_t* n_points, void* stream);
+int pnr_tsdf_extract_emit(const pnr_tsdf* vol, const void* ws, size_t ws_bytes, float* xyz, float* rgb, void* stream);
+
 /* ---- two-way descriptor matching (src/Tracker.py:398-440, nn_match_two_way; additions to ABI 14) ----
  * desc1 (D,N), desc2 (D,M): float32 row-major with unit-norm columns (the reference's SuperPoint layout);
  * D a multiple of 32 in [32, 512], N, M <= 2^20.  dot = desc1^T desc2 on v_mfma_f32_32x32x2_f32 (each

@@ -92,6 +92,12 @@ int launch_bound_support(const pnr_bound_frames&, const float*, int32_t, float*,
 int launch_bound_points(const pnr_bound_frames&, const int64_t*, int64_t, float*, hipStream_t);
 int launch_bound_contains_f32(const float*, int64_t, const double*, int32_t, uint8_t*, hipStream_t);
 int launch_bound_contains_f64(const double*, int64_t, const double*, int32_t, uint8_t*, hipStream_t);
+size_t tsdf_directory_bytes(const pnr_tsdf*);
+size_t tsdf_workspace_bytes(const pnr_tsdf*);
+int launch_tsdf_reset(const pnr_tsdf*, hipStream_t);
+int launch_tsdf_integrate(const pnr_tsdf*, const float*, const float*, const float*, int32_t, void*, size_t, hipStream_t);
+int launch_tsdf_extract_count(const pnr_tsdf*, void*, size_t, int64_t*, hipStream_t);
+int launch_tsdf_extract_emit(const pnr_tsdf*, const void*, size_t, float*, float*, hipStream_t);
 size_t match_workspace_bytes(int64_t, int64_t);
 int launch_match_two_way(const float*, const float*, int32_t, int64_t, int64_t, float, int32_t*, int32_t*, float*,
                          int32_t*, void*, size_t, hipStream_t);
@@ -1640,6 +1646,26 @@ int pnr_bound_contains_f32(const float* p, int64_t P, const double* planes, int3
 int pnr_bound_contains_f64(const double* p, int64_t P, const double* planes, int32_t F, uint8_t* inside,
                            void* stream) {
   return launch_bound_contains_f64(p, P, planes, F, inside, (hipStream_t)stream);
+}
+
+// ---- block-sparse TSDF volume (tsdf.hip; Mesher.py:231-266) -------------------------------------------
+size_t pnr_tsdf_directory_bytes(const pnr_tsdf* vol) { return tsdf_directory_bytes(vol); }
+
+size_t pnr_tsdf_workspace_bytes(const pnr_tsdf* vol) { return tsdf_workspace_bytes(vol); }
+
+int pnr_tsdf_reset(const pnr_tsdf* vol, void* stream) { return launch_tsdf_reset(vol, (hipStream_t)stream); }
+
+int pnr_tsdf_integrate(const pnr_tsdf* vol, const float* depth, const float* color, const float* c2w, int32_t K,
+                       void* ws, size_t ws_bytes, void* stream) {
+  return launch_tsdf_integrate(vol, depth, color, c2w, K, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int pnr_tsdf_extract_count(const pnr_tsdf* vol, void* ws, size_t ws_bytes, int64_t* n_points, void* stream) {
+  return launch_tsdf_extract_count(vol, ws, ws_bytes, n_points, (hipStream_t)stream);
+}
+
+int pnr_tsdf_extract_emit(const pnr_tsdf* vol, const void* ws, size_t ws_bytes, float* xyz, float* rgb, void* stream) {
+  return launch_tsdf_extract_emit(vol, ws, ws_bytes, xyz, rgb, (hipStream_t)stream);
 }
 
 // ---- two-way descriptor matching (match.hip; Tracker.py:398-440) --------------------------------------

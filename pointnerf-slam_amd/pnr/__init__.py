@@ -18,6 +18,8 @@ from . import relpose
 from .relpose import estimate_pose
 from .mapping import BundleAdjust, MapGraph, MapStep, WindowSampler
 from . import mesher, logger
+from . import tsdf
+from .tsdf import TSDFVolume
 from .logger import Logger, load_ckpt
 from .mesher import Mesher
 
@@ -26,7 +28,7 @@ __all__ = ['Renderer', 'MLP', 'PARAM_ORDER', 'FC_ORDER', 'NeuralPoints', 'get_mo
            'quad2rotation', 'TrackStep', 'track_frame', 'get_samples', 'random_select', 'mesher', 'logger', 'Logger',
            'load_ckpt', 'Mesher', 'BundleAdjust', 'MapGraph', 'MapStep', 'WindowSampler', 'matching', 'match_two_way',
            'nn_match_two_way', 'superpoint', 'SuperPointNet', 'SuperPointFrontend', 'relpose',
-           'estimate_pose']
+           'estimate_pose', 'tsdf', 'TSDFVolume']
 
 
 def library():

@@ -97,7 +97,19 @@ class BoundFrames(ctypes.Structure):
     ]
 
 
+class Tsdf(ctypes.Structure):
+    """Mirror of `pnr_tsdf` (include/pnr.h)."""
+    _fields_ = [
+        ('origin', c_float * 3), ('voxel_length', c_float), ('sdf_trunc', c_float), ('depth_trunc', c_float),
+        ('dims', c_int32 * 3), ('max_blocks', c_int32), ('H', c_int32), ('W', c_int32),
+        ('fx', c_float), ('fy', c_float), ('cx', c_float), ('cy', c_float),
+        ('directory', c_void_p), ('tsdf', c_void_p), ('weight', c_void_p), ('rgb', c_void_p),
+        ('block_index', c_void_p),
+    ]
+
+
 PBoundFrames = ctypes.POINTER(BoundFrames)
+PTsdf = ctypes.POINTER(Tsdf)
 PtrArray = c_void_p * N_PARAMS
 FcPtrArray = c_void_p * N_FC_PARAMS
 PPoints = ctypes.POINTER(Points)
@@ -227,6 +239,12 @@ _SIGS = {
     'pnr_bound_points': (ctypes.c_int, [PBoundFrames, c_void_p, c_int64, c_void_p, c_void_p]),
     'pnr_bound_contains_f32': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
     'pnr_bound_contains_f64': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
+    'pnr_tsdf_directory_bytes': (c_size_t, [PTsdf]),
+    'pnr_tsdf_workspace_bytes': (c_size_t, [PTsdf]),
+    'pnr_tsdf_reset': (ctypes.c_int, [PTsdf, c_void_p]),
+    'pnr_tsdf_integrate': (ctypes.c_int, [PTsdf, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
+    'pnr_tsdf_extract_count': (ctypes.c_int, [PTsdf, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'pnr_tsdf_extract_emit': (ctypes.c_int, [PTsdf, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     'pnr_match_workspace_bytes': (c_size_t, [c_int64, c_int64]),
     'pnr_match_two_way': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int64, c_float, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

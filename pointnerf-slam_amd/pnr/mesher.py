@@ -21,10 +21,12 @@ host libraries for it (skimage, trimesh, open3d) are not importable on this stac
     -- the support function of the back-projected depth pixels, the positions of chosen points and the
     containment test on the device (csrc/bound.hip), the quickhull between them on the host
     (pnr/bound.py) -- applied by get_mesh with `mesh_bound_mask='frames'`;
+    with `surface='tsdf'` (get_mesh: `mesh_bound_mask='tsdf'`) the hull is taken, as in the reference, over
+    the surface points of a block-sparse TSDF volume fused from the keyframes (csrc/tsdf.hip, pnr/tsdf.py);
   * `write_ply`, and `Mesher.get_mesh` that strings everything together.
 Stated deviations.  Components rule: components are taken over shared VERTICES, trimesh.split takes
 them over shared edges: the two differ only where components touch at a single vertex.  Depth pixels,
-not a TSDF surface: the reference's hull is taken over the vertices of an open3d TSDF surface (voxel
+not a TSDF surface (the default; `surface='tsdf'` fuses one): the reference's hull is taken over the vertices of an open3d TSDF surface (voxel
 4 scale / 512) fused from the depth maps, ours over the valid depth pixels themselves and the camera
 centres; the two hulls differ by the order of that voxel, and parity with open3d is unpinned, as for
 `vertex_normals`.  A hull to a tolerance: refinement stops when no point lies more than eps / 2
@@ -320,12 +322,20 @@ class FrameBound(object):
 
 
 def get_bound_from_frames(keyframe_dict, H, W, fx, fy, cx, cy, scale=1.0, bound_scale=1.02, device='cuda:0',
-                          stride=1, eps=None, max_facets=16384):
+                          stride=1, eps=None, max_facets=16384, surface='pixels', max_blocks=32768):
     """src/utils/Mesher.py:214-279 on the device: the FrameBound of the keyframes' 'depth' (H,W) and
     'est_c2w' (4,4).  `eps` defaults to the reference's TSDF voxel 4 scale / 512; `stride` >= 1 thins the
-    pixels to a lattice.  One small host read per refinement round, as marching cubes reads its counts."""
+    pixels to a lattice.  One small host read per refinement round, as marching cubes reads its counts.
+
+    surface='pixels' (the default) takes the hull over the depth pixels themselves.  surface='tsdf' takes it, as
+    the reference does, over the surface of a TSDF volume fused from the keyframes (pnr.tsdf.TSDFVolume, voxel
+    4 scale / 512, truncation 0.04 scale, `max_blocks` slots) over the axis-aligned box of the depth pixels -- one
+    support launch over the six axis directions -- plus the camera centres; the volume is returned as
+    `fb.volume`, and stats gains surface_points, tsdf_blocks and tsdf_dropped_blocks."""
     if len(keyframe_dict) == 0:
         raise ValueError('pnr.mesher: get_bound_from_frames needs at least one keyframe')
+    if surface not in ('pixels', 'tsdf'):
+        raise ValueError(f"pnr.mesher: surface {surface!r} (one of 'pixels', 'tsdf')")
     device = torch.device(device)
     depth = torch.stack([kf['depth'].to(device).reshape(H, W) for kf in keyframe_dict]).float()
     c2w = torch.stack([torch.as_tensor(kf['est_c2w']).detach().to(device).float().reshape(4, 4)
@@ -335,9 +345,24 @@ def get_bound_from_frames(keyframe_dict, H, W, fx, fy, cx, cy, scale=1.0, bound_
     if not bool((torch.isfinite(lattice) & (lattice > 0) & (lattice <= DEPTH_TRUNC)).any()):
         raise ValueError('pnr.mesher: get_bound_from_frames found no valid depth pixel')
     eps =4.0 * float(scale) / 512.0 if eps is None else float(eps)
+    launches, vol = 0, None
+    if surface == 'tsdf':
+        from .tsdf import TSDFVolume
+        h = pts.support_np(np.concatenate([np.eye(3), -np.eye(3)]).astype(np.float32))[0].astype(np.float64)
+        box = np.stack([-h[3:], h[:3]], 1)
+        vol = TSDFVolume(box, 4.0 * float(scale) / 512.0, 0.04 * float(scale), H, W, fx, fy, cx, cy, max_blocks,
+                         depth_trunc=DEPTH_TRUNC, device=device, color=False)
+        vol.integrate(depth, None, c2w)
+        surf = vol.extract_points()[0]
+        launches = pts.support_launches
+        pts = FramePoints(depth[:0], c2w[:0], fx, fy, cx, cy, extra=torch.cat([surf, c2w[:, :3, 3]]))
     hull = _bound.build_hull(pts.support_np, pts.points_np, eps, max_facets)
     fb = FrameBound(hull, bound_scale, eps, device)
-    fb.stats['support_launches'] = pts.support_launches
+    fb.stats['support_launches'] = pts.support_launches + launches
+    if vol is not None:
+        fb.volume = vol
+        fb.stats.update(surface_points=int(surf.shape[0]), tsdf_blocks=vol.n_blocks,
+                        tsdf_dropped_blocks=vol.dropped_blocks)
     return fb
 
 
@@ -526,7 +551,7 @@ class Mesher(object):
 
     def get_bound_from_frames(self, keyframe_dict, scale=1, device='cuda:0', **kw):
         """Mesher.get_bound_from_frames (:214-279): the FrameBound of the keyframes, scaled by
-        clean_mesh_bound_scale about its centre.  `kw`: stride, eps, max_facets."""
+        clean_mesh_bound_scale about its centre.  `kw`: stride, eps, max_facets, surface, max_blocks."""
         return get_bound_from_frames(keyframe_dict, self.H, self.W, self.fx, self.fy, self.cx, self.cy, scale=scale,
                                      bound_scale=self.clean_mesh_bound_scale, device=device, **kw)
 
@@ -539,16 +564,17 @@ class Mesher(object):
 
         `mesh_bound_mask` is the reference's convex hull (get_bound_from_frames, :421 / :475):
         'frames' builds the FrameBound of `keyframe_dict` at self.scale, as the reference does in every
-        extraction; a FrameBound or any callable points (N,3) -> bool (N,) is used as given; a bool
+        extraction ('tsdf': over the fused TSDF surface, get_bound_from_frames(surface='tsdf')); a FrameBound or any callable points (N,3) -> bool (N,) is used as given; a bool
         tensor over the grid points masks the grid alone.  With show_forecast=False it sets the occupancy
         outside it to 100 (:433); with show_forecast=True a callable also culls the faces whose vertices
         all lie outside it (:475-485).  None (the default) applies no hull mask."""
         with torch.no_grad():
             device = torch.device(device)
             if isinstance(mesh_bound_mask, str):
-                if mesh_bound_mask != 'frames':
-                    raise ValueError(f"pnr.mesher: mesh_bound_mask {mesh_bound_mask!r} (the only name is 'frames')")
-                mesh_bound_mask = self.get_bound_from_frames(keyframe_dict, self.scale, device=device)
+                if mesh_bound_mask not in ('frames', 'tsdf'):
+                    raise ValueError(f"pnr.mesher: mesh_bound_mask {mesh_bound_mask!r} (the names are 'frames', 'tsdf')")
+                mesh_bound_mask = self.get_bound_from_frames(
+                    keyframe_dict, self.scale, device=device, surface='tsdf' if mesh_bound_mask == 'tsdf' else 'pixels')
             grid = self.get_grid_uniform(self.resolution)
             points = grid['grid_points'].to(device)
             masks = dict(keyframe_dict=keyframe_dict, estimate_c2w_list=estimate_c2w_list, idx=idx, device=device,
