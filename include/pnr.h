@@ -803,6 +803,63 @@ size_t pnr_paint_depth_workspace_bytes(int32_t H, int32_t W);
 int pnr_paint_depth(const double* uv, const double* depth, int64_t n, int32_t H, int32_t W, int32_t patch, float* out,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- reconstruction metrics (src/tools/eval_recon.py calc_3d_metric; additions to ABI 14) ------------------
+ * All float64; point sets are (n,3) row-major.  Sizes up to 2^28 points.
+ *
+ * Exact nearest neighbour by brute force over all Q R pairs on the float64 MFMA.  dist (Q) and idx (Q) int64:
+ *  - dist[i] is the float64 distance |query[i] - ref[idx[i]]| from coordinate differences,
+ *    sqrt((dx dx + dy dy) + dz dz) with every operation rounded once: exact to rounding.
+ *  - idx[i] is chosen by the expansion d^2 = |a|^2 + (|b|^2 - 2 a.b) over the clouds centred on the query's
+ *    bounding-box centre, compared on its leading 28 mantissa bits, ties to the lower index.  Its squared
+ *    distance is at most d^2_min (1 + 2^-27) + 2 E with E = 16 * 2^-53 * max (|a| + |b|)^2 over the centred
+ *    clouds, the rounding bound of the four-term expansion.  Wherever the runner-up is farther than that,
+ *    idx[i] is the argmin.
+ *  - With max_dist finite, a query whose chosen point is farther than max_dist (dist <= max_dist keeps it) gets
+ *    idx -1 and dist +inf.  Pass +inf for no limit; a negative or NaN max_dist is PNR_E_ARG.
+ *  - Equal arguments give equal bits, whatever the slice count.  slices = 0 lets the call split the ref columns
+ *    over workgroups as it sees fit (small Q still fills the chip); 1 <= slices <= min(chunks of 512 ref
+ *    points, max(automatic count, 4)) forces a count (larger: PNR_E_ARG).
+ *  - Q = 0 or R = 0 launches nothing and writes nothing.  Non-finite coordinates are the caller's fault: the
+ *    outputs are then unspecified, but every access stays in bounds.
+ * workspace: pnr_nn_workspace_bytes(Q, R) bytes (0 for sizes the call refuses), 16-byte aligned, any contents. */
+size_t pnr_nn_workspace_bytes(int64_t Q, int64_t R);
+int pnr_nn_search(const double* query, int64_t Q, const double* ref, int64_t R, double max_dist, int32_t slices,
+                  double* dist, int64_t* idx, void* workspace, size_t workspace_bytes, void* stream);
+/* Surface sampling by trimesh.sample.sample_surface's rule.  verts (V,3), faces (F,3) int64.
+ * pnr_face_areas: area (F) = half the cross-product norm; a face with an index outside [0, V) has area 0.
+ * pnr_sample_surface: cum_area (F) is the inclusive prefix sum of the areas (the caller's scan).  Sample i
+ * takes uniforms (u0, u1, u2) in [0, 1): row i of `uniforms` (count,3) when it is given, else
+ *   base = mix(seed * 0x9E3779B97F4A7C15), u_k = (mix(base + (3 i + k) * 0xD1B54A32D192ED03) >> 11) * 2^-53
+ * with mix the splitmix64 finaliser (as in pnr_relpose_estimate), so the samples depend on (seed, i) alone.
+ * The face is the first with cum_area >= u0 * total and cum_area > 0 (never a zero-area face); (u1, u2) become
+ * (1 - u1, 1 - u2) when u1 + u2 > 1; the point is ((v1 - v0) u1 + (v2 - v0) u2) + v0, unfused.  points
+ * (count,3), face_idx (count) int64.  A total area that is zero or not finite gives NaN points and face -1.
+ * The rule is trimesh's; its random stream is not reproduced (numpy's generator is not built). */
+int pnr_face_areas(const double* verts, int64_t V, const int64_t* faces, int64_t F, double* area, void* stream);
+int pnr_sample_surface(const double* verts, const int64_t* faces, const double* cum_area, int64_t F, int64_t count,
+                       uint64_t seed, const double* uniforms, double* points, int64_t* face_idx, void* stream);
+/* out[0] = the sum of dist (n), out[1] = the number of entries < dist_th, both summed in float64 in a fixed
+ * order (per-block partials, then one block): equal arguments give equal bits.  1 <= n <= 2^28.
+ * workspace: pnr_dist_stats_workspace_bytes() bytes, 8-byte aligned, any contents. */
+size_t pnr_dist_stats_workspace_bytes(void);
+int pnr_dist_stats(const double* dist, int64_t n, double dist_th, double* out, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* out (n,3) = R p + t for T = [R t; 0 1] (4,4) row-major on the device; out is a buffer of its own. */
+int pnr_transform_points(const double* pts, int64_t n, const double* T, double* out, void* stream);
+/* One step of point-to-point ICP (open3d registration_icp): src (N,3) is moved by T_in, every moved point
+ * takes its nearest dst (M,3) point within `threshold` (pnr_nn_search with max_dist = threshold), and
+ * stats (3) = fitness (matched / N), inlier RMSE (0 without a match), matched count describe T_in.
+ * T_out = [R t; 0 1] T_in where (R, t) is the least-squares rigid motion of the matched pairs: Kabsch on the
+ * cross-covariance about the centroids, sums in a fixed order, SVD by one-sided Jacobi, the weakest singular
+ * pair replaced by cross products so that det R = +1 (the reflection fix).  No match: T_out = T_in.  T_in and
+ * T_out are distinct (4,4) row-major device matrices.  The caller iterates and tests convergence.
+ * workspace: pnr_icp_workspace_bytes(N, M) bytes (0 for sizes the call refuses), 16-byte aligned, any
+ * contents; afterwards it starts with the moved points (N,3), then dist (N) and idx (N) int64 from byte
+ * offsets round16(24 N) and round16(24 N) + round16(8 N). */
+size_t pnr_icp_workspace_bytes(int64_t N, int64_t M);
+int pnr_icp_step(const double* src, int64_t N, const double* dst, int64_t M, const double* T_in, double threshold,
+                 double* T_out, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- diagnostics (not on the reference API) ----------------------------------------------- */
 /* Kernel timing: while enabled, every launch of the timed kernels is bracketed by hipEvents on
  * its own stream.  pnr_timing_read synchronises those events and returns, for `kernel`

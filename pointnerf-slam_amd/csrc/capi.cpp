@@ -115,6 +115,18 @@ int launch_triangulate(const double*, const double*, const double*, const double
 size_t paint_depth_workspace_bytes(int32_t, int32_t);
 int launch_paint_depth(const double*, const double*, int64_t, int32_t, int32_t, int32_t, float*, void*, size_t,
                        hipStream_t);
+size_t nn_workspace_bytes(int64_t, int64_t);
+int launch_nn_search(const double*, int64_t, const double*, int64_t, double, int32_t, double*, int64_t*, void*, size_t,
+                     hipStream_t);
+int launch_face_areas(const double*, int64_t, const int64_t*, int64_t, double*, hipStream_t);
+int launch_sample_surface(const double*, const int64_t*, const double*, int64_t, int64_t, uint64_t, const double*,
+                          double*, int64_t*, hipStream_t);
+size_t dist_stats_workspace_bytes();
+int launch_dist_stats(const double*, int64_t, double, double*, void*, size_t, hipStream_t);
+int launch_transform_points(const double*, int64_t, const double*, double*, hipStream_t);
+size_t icp_workspace_bytes(int64_t, int64_t);
+int launch_icp_step(const double*, int64_t, const double*, int64_t, const double*, double, double*, double*, void*,
+                    size_t, hipStream_t);
 
 }  // namespace pnr
 
@@ -1703,6 +1715,42 @@ size_t pnr_paint_depth_workspace_bytes(int32_t H, int32_t W) { return paint_dept
 int pnr_paint_depth(const double* uv, const double* depth, int64_t n, int32_t H, int32_t W, int32_t patch, float* out,
                     void* workspace, size_t workspace_bytes, void* stream) {
   return launch_paint_depth(uv, depth, n, H, W, patch, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- reconstruction metrics (recon.hip; src/tools/eval_recon.py) -----------------------------------------------
+size_t pnr_nn_workspace_bytes(int64_t Q, int64_t R) { return nn_workspace_bytes(Q, R); }
+
+int pnr_nn_search(const double* query, int64_t Q, const double* ref, int64_t R, double max_dist, int32_t slices,
+                  double* dist, int64_t* idx, void* workspace, size_t workspace_bytes, void* stream) {
+  return launch_nn_search(query, Q, ref, R, max_dist, slices, dist, idx, workspace, workspace_bytes,
+                          (hipStream_t)stream);
+}
+
+int pnr_face_areas(const double* verts, int64_t V, const int64_t* faces, int64_t F, double* area, void* stream) {
+  return launch_face_areas(verts, V, faces, F, area, (hipStream_t)stream);
+}
+
+int pnr_sample_surface(const double* verts, const int64_t* faces, const double* cum_area, int64_t F, int64_t count,
+                       uint64_t seed, const double* uniforms, double* points, int64_t* face_idx, void* stream) {
+  return launch_sample_surface(verts, faces, cum_area, F, count, seed, uniforms, points, face_idx, (hipStream_t)stream);
+}
+
+size_t pnr_dist_stats_workspace_bytes(void) { return dist_stats_workspace_bytes(); }
+
+int pnr_dist_stats(const double* dist, int64_t n, double dist_th, double* out, void* workspace, size_t workspace_bytes,
+                   void* stream) {
+  return launch_dist_stats(dist, n, dist_th, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int pnr_transform_points(const double* pts, int64_t n, const double* T, double* out, void* stream) {
+  return launch_transform_points(pts, n, T, out, (hipStream_t)stream);
+}
+
+size_t pnr_icp_workspace_bytes(int64_t N, int64_t M) { return icp_workspace_bytes(N, M); }
+
+int pnr_icp_step(const double* src, int64_t N, const double* dst, int64_t M, const double* T_in, double threshold,
+                 double* T_out, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  return launch_icp_step(src, N, dst, M, T_in, threshold, T_out, stats, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- SuperPoint (conv.hip, keypoints.hip; demo_superpoint.py:78-293) ----------------------------------

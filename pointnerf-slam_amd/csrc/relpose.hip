@@ -31,6 +31,7 @@
 //                       one-sided (Hestenes) Jacobi on A itself, and the two projections K (Rcw p + tcw).
 //   k_paint_*           the pseudo-depth map: clear owners, atomicMax of i + 1 over each point's pixels, resolve.
 // Integer atomics only, vector stores only.
+#include "jacobi.h"
 #include "pnr_internal.h"
 
 namespace pnr {
@@ -50,45 +51,6 @@ __device__ __forceinline__ T sel(const T (&a)[N], int i) {
 #pragma unroll
   for (int c = 1; c < N; ++c) v = c == i ? a[c] : v;
   return v;
-}
-
-// One-sided Jacobi: rotates the columns of A until they are orthogonal; A <- U S, V accumulates.
-template <int N>
-__device__ __forceinline__ void jacobi(double (&A)[N][N], double (&V)[N][N]) {
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-#pragma unroll
-    for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 20; ++sweep) {
-    bool any = false;
-#pragma unroll
-    for (int p = 0; p < N - 1; ++p)
-#pragma unroll
-      for (int q = p + 1; q < N; ++q) {
-        double al = 0.0, be = 0.0, g = 0.0;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-          al += A[i][p] * A[i][p];
-          be += A[i][q] * A[i][q];
-          g += A[i][p] * A[i][q];
-        }
-        if (fabs(g) > 2.3e-16 * sqrt(al * be)) {
-          any = true;
-          const double zeta = (be - al) / (2.0 * g);
-          const double tt = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-          const double c = 1.0 / sqrt(1.0 + tt * tt), s = c * tt;
-#pragma unroll
-          for (int i = 0; i < N; ++i) {
-            const double ap = A[i][p], aq = A[i][q], vp = V[i][p], vq = V[i][q];
-            A[i][p] = c * ap - s * aq;
-            A[i][q] = s * ap + c * aq;
-            V[i][p] = c * vp - s * vq;
-            V[i][q] = s * vp + c * vq;
-          }
-        }
-      }
-    if (!any) break;
-  }
 }
 
 // DLT of utils_geom.py:140-147: rows x P[2] - P[0], y P[2] - P[1] of both views; X = the right singular vector

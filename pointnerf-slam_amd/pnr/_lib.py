@@ -263,6 +263,18 @@ _SIGS = {
     'pnr_paint_depth_workspace_bytes': (c_size_t, [c_int32, c_int32]),
     'pnr_paint_depth': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                        c_size_t, c_void_p]),
+    'pnr_nn_workspace_bytes': (c_size_t, [c_int64, c_int64]),
+    'pnr_nn_search': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, ctypes.c_double, c_int32, c_void_p, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
+    'pnr_face_areas': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    'pnr_sample_surface': (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_uint64, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
+    'pnr_dist_stats_workspace_bytes': (c_size_t, []),
+    'pnr_dist_stats': (ctypes.c_int, [c_void_p, c_int64, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'pnr_transform_points': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'pnr_icp_workspace_bytes': (c_size_t, [c_int64, c_int64]),
+    'pnr_icp_step': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, ctypes.c_double, c_void_p, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
     'pnr_timing_enable': (ctypes.c_int, [ctypes.c_int]),
     'pnr_timing_read': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_int64), ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(c_int64)]),
