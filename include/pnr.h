@@ -860,6 +860,75 @@ size_t pnr_icp_workspace_bytes(int64_t N, int64_t M);
 int pnr_icp_step(const double* src, int64_t N, const double* dst, int64_t M, const double* T_in, double threshold,
                  double* T_out, double* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- mesh depth rasteriser (src/tools/eval_recon.py calc_2d_metric, check_proj; src/tools/cull_mesh.py;
+ * additions to ABI 14) ------------------------------------------------------------------------------------------
+ * Depth images of a triangle mesh, float64 arithmetic, float32 images.  The rendering rule:
+ *  - Camera.  c2w (n,4,4) row-major float64 = [R t] per view with OpenCV axes (x right, y down, z forward), what
+ *    calc_2d_metric hands open3d as inv(extrinsic).  R is taken as orthonormal: a world point x has camera
+ *    coordinates p = R^T (x - t), each component ((r0 d0 + r1 d1) + r2 d2) with d = x - t.  The last row is not read.
+ *  - Projection.  p = (x, y, z) has homogeneous image coordinates q = (fx x + cx z, fy y + cy z, z).
+ *  - Pixels.  The centre of pixel (row i, column j) is s = (j, i, 1): integer coordinates are pixel centres
+ *    (cx = W / 2 - 0.5 centres the image).
+ *  - Homogeneous edge functions (Olano-Greer): nothing is clipped at the near plane for coverage.  For a face
+ *    with vertices 0, 1, 2 the edge opposite vertex k has E_k(s) = (q_i x q_j) . s with (i, j) = (k + 1, k + 2)
+ *    mod 3, evaluated (n_x j + n_y i) + n_z, and det = q_0 . (q_1 x q_2) = (q0_x n_x + q0_y n_y) + q0_z n_z.  The
+ *    pixel is covered iff det != 0 and E_k sign(det) >= 0 for k = 0, 1, 2; its depth is
+ *    z = det / ((E_0 + E_1) + E_2); the sample is kept iff z_near <= z <= z_far.
+ *  - Output.  depth[view][i][j] is the least kept z over all faces, rounded once to float32; 0 without one.
+ *  - Two-sided: both orientations render (the reference's mesh_show_back_face = True).
+ *  - A face with a vertex index outside [0, V) or with det = 0 contributes nothing.
+ *  - Watertight.  An edge's cross product is formed with the lower vertex index first and negated if that
+ *    swapped the operands, so the two faces of a shared edge see exactly negated edge values and no pixel centre
+ *    falls between them; a centre exactly on the edge is covered by both, harmless under a minimum.
+ *  - Reproducible.  A minimum: equal arguments give equal bits, whatever the view batch and the bin order.
+ *  - Every operation is rounded once (no fused multiply-add).  Non-finite coordinates are the caller's fault:
+ *    the image is then unspecified, but every access stays in bounds.
+ * Deviations from open3d's OpenGL capture, stated: z_near is a parameter (calc_2d_metric's default here 0.01;
+ * open3d derives its own from the scene) and must be > 0; z_far (finite, >= z_near) defaults to 20, the
+ * reference's set_constant_z_far; the background is 0; no anti-aliasing and no top-left fill rule.
+ *
+ * Three calls render the n_views of a pnr_raster, with 32 x 32-pixel tiles, T = ceil(W / 32) ceil(H / 32):
+ *   pnr_raster_count   counts (n_views T) int32 = per (view, tile) the faces whose conservative pixel box (of
+ *                      the part with z >= z_near, widened by 2^-8 pixel, clamped to the image) overlaps the tile.
+ *   (the caller)       ends (n_views T) int64 = the inclusive prefix sum of counts; pairs = its last entry.
+ *   pnr_raster_fill    the face ids into the tile lists of the workspace (list order depends on scheduling).
+ *   pnr_raster_tiles   depth (n_views, H, W) float32 from the lists; every pixel is written.
+ * counts, ends and pairs of fill and tiles are those of the count call on the same pnr_raster; other values
+ * leave the image unspecified and every access in bounds.  1 <= n_views <= 4096, 1 <= H, W <= 8192,
+ * n_views T <= 2^24, V, F <= 2^28, pairs <= 2^30: otherwise PNR_E_ARG, and pnr_raster_counters and
+ * pnr_raster_workspace_bytes return 0.  The caller batches the views to stay inside those bounds.
+ * workspace: pnr_raster_workspace_bytes(r, pairs) bytes, 16-byte aligned, any contents before fill; tiles reads
+ * what fill left. */
+typedef struct pnr_raster {
+  const double* verts; /* (V,3) */
+  int64_t V;
+  const int64_t* faces; /* (F,3) */
+  int64_t F;
+  const double* c2w; /* (n_views,4,4) */
+  int32_t n_views, H, W, reserved;
+  double fx, fy, cx, cy, z_near, z_far;
+} pnr_raster;
+int64_t pnr_raster_counters(const pnr_raster* r); /* n_views T */
+size_t pnr_raster_workspace_bytes(const pnr_raster* r, int64_t pairs);
+int pnr_raster_count(const pnr_raster* r, int32_t* counts, void* stream);
+int pnr_raster_fill(const pnr_raster* r, const int32_t* counts, const int64_t* ends, int64_t pairs, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int pnr_raster_tiles(const pnr_raster* r, const int32_t* counts, const int64_t* ends, int64_t pairs, float* depth,
+                     const void* workspace, size_t workspace_bytes, void* stream);
+/* out (n) float64 = per image the mean of |a - b| over its hw pixels: a, b (n, hw) float32, differences and sums
+ * in float64 in a fixed order (per-block partials, then one block): equal arguments give equal bits.
+ * 1 <= n <= 65535, 1 <= hw <= 2^26.  workspace: pnr_depth_l1_workspace_bytes(n) bytes, 8-byte aligned. */
+size_t pnr_depth_l1_workspace_bytes(int64_t n);
+int pnr_depth_l1(const float* a, const float* b, int64_t n, int64_t hw, double* out, void* workspace,
+                 size_t workspace_bytes, void* stream);
+/* check_proj's frustum test for every (point, view): with p and q as above, zz = z + 1e-5, the view sees the
+ * point iff zz > 0, 0 < q_x / zz < W and 0 < q_y / zz < H.  view_any (n) uint8 = 1 where the view sees any of
+ * the points (the view sampler's rejection), point_any (P) uint8 = 1 where any view sees the point
+ * (cull_mesh.py), else 0; either may be null.  Float64 where the reference computes in float32, and OpenCV
+ * poses where it flips an OpenGL pose: its guard is z - 1e-5 >= 0 on the same axis. */
+int pnr_frustum_seen(const double* points, int64_t P, const double* c2w, int32_t n, int32_t H, int32_t W, double fx,
+                     double fy, double cx, double cy, uint8_t* view_any, uint8_t* point_any, void* stream);
+
 /* ---- diagnostics (not on the reference API) ----------------------------------------------- */
 /* Kernel timing: while enabled, every launch of the timed kernels is bracketed by hipEvents on
  * its own stream.  pnr_timing_read synchronises those events and returns, for `kernel`

@@ -127,6 +127,16 @@ int launch_transform_points(const double*, int64_t, const double*, double*, hipS
 size_t icp_workspace_bytes(int64_t, int64_t);
 int launch_icp_step(const double*, int64_t, const double*, int64_t, const double*, double, double*, double*, void*,
                     size_t, hipStream_t);
+int64_t raster_counters(const pnr_raster*);
+size_t raster_workspace_bytes(const pnr_raster*, int64_t);
+int launch_raster_count(const pnr_raster*, int32_t*, hipStream_t);
+int launch_raster_fill(const pnr_raster*, const int32_t*, const int64_t*, int64_t, void*, size_t, hipStream_t);
+int launch_raster_tiles(const pnr_raster*, const int32_t*, const int64_t*, int64_t, float*, const void*, size_t,
+                        hipStream_t);
+size_t depth_l1_workspace_bytes(int64_t);
+int launch_depth_l1(const float*, const float*, int64_t, int64_t, double*, void*, size_t, hipStream_t);
+int launch_frustum_seen(const double*, int64_t, const double*, int32_t, int32_t, int32_t, double, double, double,
+                        double, uint8_t*, uint8_t*, hipStream_t);
 
 }  // namespace pnr
 
@@ -1751,6 +1761,37 @@ size_t pnr_icp_workspace_bytes(int64_t N, int64_t M) { return icp_workspace_byte
 int pnr_icp_step(const double* src, int64_t N, const double* dst, int64_t M, const double* T_in, double threshold,
                  double* T_out, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
   return launch_icp_step(src, N, dst, M, T_in, threshold, T_out, stats, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- mesh depth rasteriser (raster.hip; src/tools/eval_recon.py calc_2d_metric, cull_mesh.py) -------------------
+int64_t pnr_raster_counters(const pnr_raster* r) { return raster_counters(r); }
+
+size_t pnr_raster_workspace_bytes(const pnr_raster* r, int64_t pairs) { return raster_workspace_bytes(r, pairs); }
+
+int pnr_raster_count(const pnr_raster* r, int32_t* counts, void* stream) {
+  return launch_raster_count(r, counts, (hipStream_t)stream);
+}
+
+int pnr_raster_fill(const pnr_raster* r, const int32_t* counts, const int64_t* ends, int64_t pairs, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  return launch_raster_fill(r, counts, ends, pairs, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int pnr_raster_tiles(const pnr_raster* r, const int32_t* counts, const int64_t* ends, int64_t pairs, float* depth,
+                     const void* workspace, size_t workspace_bytes, void* stream) {
+  return launch_raster_tiles(r, counts, ends, pairs, depth, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t pnr_depth_l1_workspace_bytes(int64_t n) { return depth_l1_workspace_bytes(n); }
+
+int pnr_depth_l1(const float* a, const float* b, int64_t n, int64_t hw, double* out, void* workspace,
+                 size_t workspace_bytes, void* stream) {
+  return launch_depth_l1(a, b, n, hw, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int pnr_frustum_seen(const double* points, int64_t P, const double* c2w, int32_t n, int32_t H, int32_t W, double fx,
+                     double fy, double cx, double cy, uint8_t* view_any, uint8_t* point_any, void* stream) {
+  return launch_frustum_seen(points, P, c2w, n, H, W, fx, fy, cx, cy, view_any, point_any, (hipStream_t)stream);
 }
 
 // ---- SuperPoint (conv.hip, keypoints.hip; demo_superpoint.py:78-293) ----------------------------------

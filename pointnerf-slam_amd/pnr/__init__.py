@@ -22,7 +22,7 @@ from . import tsdf
 from .tsdf import TSDFVolume
 from .logger import Logger, load_ckpt
 from . import recon
-from .recon import calc_3d_metric
+from .recon import calc_2d_metric, calc_3d_metric
 from .mesher import Mesher
 
 __all__ = ['Renderer', 'MLP', 'PARAM_ORDER', 'FC_ORDER', 'NeuralPoints', 'get_model', 'load_config', 'ROOM0_CFG', 'get_rays',
@@ -30,7 +30,7 @@ __all__ = ['Renderer', 'MLP', 'PARAM_ORDER', 'FC_ORDER', 'NeuralPoints', 'get_mo
            'quad2rotation', 'TrackStep', 'track_frame', 'get_samples', 'random_select', 'mesher', 'logger', 'Logger',
            'load_ckpt', 'Mesher', 'BundleAdjust', 'MapGraph', 'MapStep', 'WindowSampler', 'matching', 'match_two_way',
            'nn_match_two_way', 'superpoint', 'SuperPointNet', 'SuperPointFrontend', 'relpose',
-           'estimate_pose', 'tsdf', 'TSDFVolume', 'recon', 'calc_3d_metric']
+           'estimate_pose', 'tsdf', 'TSDFVolume', 'recon', 'calc_3d_metric', 'calc_2d_metric']
 
 
 def library():

@@ -108,7 +108,18 @@ class Tsdf(ctypes.Structure):
     ]
 
 
+class Raster(ctypes.Structure):
+    """Mirror of `pnr_raster` (include/pnr.h)."""
+    _fields_ = [
+        ('verts', c_void_p), ('V', c_int64), ('faces', c_void_p), ('F', c_int64), ('c2w', c_void_p),
+        ('n_views', c_int32), ('H', c_int32), ('W', c_int32), ('reserved', c_int32),
+        ('fx', ctypes.c_double), ('fy', ctypes.c_double), ('cx', ctypes.c_double), ('cy', ctypes.c_double),
+        ('z_near', ctypes.c_double), ('z_far', ctypes.c_double),
+    ]
+
+
 PBoundFrames = ctypes.POINTER(BoundFrames)
+PRaster = ctypes.POINTER(Raster)
 PTsdf = ctypes.POINTER(Tsdf)
 PtrArray = c_void_p * N_PARAMS
 FcPtrArray = c_void_p * N_FC_PARAMS
@@ -275,6 +286,16 @@ _SIGS = {
     'pnr_icp_workspace_bytes': (c_size_t, [c_int64, c_int64]),
     'pnr_icp_step': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, ctypes.c_double, c_void_p, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),
+    'pnr_raster_counters': (c_int64, [PRaster]),
+    'pnr_raster_workspace_bytes': (c_size_t, [PRaster, c_int64]),
+    'pnr_raster_count': (ctypes.c_int, [PRaster, c_void_p, c_void_p]),
+    'pnr_raster_fill': (ctypes.c_int, [PRaster, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    'pnr_raster_tiles': (ctypes.c_int, [PRaster, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'pnr_depth_l1_workspace_bytes': (c_size_t, [c_int64]),
+    'pnr_depth_l1': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'pnr_frustum_seen': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, ctypes.c_double,
+                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p,
+                                        c_void_p]),
     'pnr_timing_enable': (ctypes.c_int, [ctypes.c_int]),
     'pnr_timing_read': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_int64), ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(c_int64)]),

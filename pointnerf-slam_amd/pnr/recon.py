@@ -1,13 +1,18 @@
 """Scoring a reconstruction on the device (src/tools/eval_recon.py: `calc_3d_metric`, `accuracy`, `completion`,
-`completion_ratio`, `get_align_transformation`).
+`completion_ratio`, `get_align_transformation`, `calc_2d_metric`, `check_proj`; src/tools/cull_mesh.py).
 
 The reference aligns with open3d's point-to-point ICP, samples both surfaces with trimesh and measures with two
 scipy KD-tree queries.  Here all of it is float64 on the device (csrc/recon.hip, include/pnr.h): an exact
 brute-force nearest-neighbour search on the float64 MFMA, trimesh's sampling rule over a counter-based
 generator, fixed-order reductions and Kabsch.  Float32 inputs are widened on entry.  Deviations, stated: the
 samples follow trimesh's rule but not numpy's random stream; the ICP moves the source by the composed transform
-each iteration instead of moving it step by step; `calc_2d_metric`, mesh culling and the trajectory error are
-not built.  There is no CPU path.
+each iteration instead of moving it step by step; the trajectory error is not built.
+
+`calc_2d_metric` renders both meshes with the tiled depth rasteriser of csrc/raster.hip where the reference drives
+open3d's OpenGL window: homogeneous edge functions in float64, the least depth per pixel (include/pnr.h "mesh depth
+rasteriser" states the rule and its deviations: z_near a parameter, background 0, no anti-aliasing, no top-left
+rule).  The view draw takes axis-aligned bounds where trimesh takes oriented ones, and numpy's random stream
+where the reference mixes trimesh's and `random`.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -221,3 +226,180 @@ def calc_3d_metric(rec, gt, align=True, n_points=200000, seed=0):
     comp, ratio = _score(gt_pc, rec_pc, 0.05)  # completion and its ratio share one search
     return {'accuracy_cm': accuracy(gt_pc, rec_pc) * 100.0, 'completion_cm': comp * 100.0,
             'completion_ratio_pct': ratio * 100.0, 'transformation': T}
+
+
+def _poses(name, c2w, dev):
+    c = torch.as_tensor(c2w, dtype=torch.float64).to(dev).contiguous()
+    if c.dim() != 3 or c.shape[1:] != (4, 4):
+        raise ValueError(f'pnr.recon.{name}: c2w is (n,4,4)')
+    return c
+
+
+def render_depth(verts, faces, c2w, H, W, fx, fy, cx, cy, z_near=0.01, z_far=20.0, view_batch=None):
+    """Depth images (n, H, W) float32 of a triangle mesh from n OpenCV camera-to-world poses, on the device, by
+    the rule of include/pnr.h "mesh depth rasteriser": least depth in [z_near, z_far] per pixel centre, two-sided,
+    watertight, 0 where nothing is hit; bitwise reproducible and independent of `view_batch` (views rendered per
+    pass; by default as many as keep the tile counters and lists inside the library's bounds, at most 64).  Each
+    batch is count -> scan -> fill -> tiles and reads its (tile, face) pair count on the host once."""
+    v, f = _mesh('render_depth', verts, faces)
+    dev = v.device
+    c = _poses('render_depth', c2w, dev)
+    n, H, W = c.shape[0], int(H), int(W)
+    out = torch.zeros((n, H, W), dtype=torch.float32, device=dev)
+    if n == 0 or f.shape[0] == 0:
+        return out
+    lib = _lib.load()
+    r = _lib.Raster(verts=_lib.ptr(v), V=v.shape[0], faces=_lib.ptr(f), F=f.shape[0], H=H, W=W, fx=fx, fy=fy, cx=cx,
+                    cy=cy, z_near=z_near, z_far=z_far)
+    batch = min(n, 64) if view_batch is None else int(view_batch)
+    if batch < 1:
+        raise ValueError('pnr.recon.render_depth: view_batch is positive')
+    st = _lib.stream_of(dev)
+    i = 0
+    while i < n:
+        b = min(batch, n - i)
+        r.c2w, r.n_views = _lib.ptr(c[i:]), b
+        nc = lib.pnr_raster_counters(r)
+        pairs, nbytes = 0, 0
+        if nc:
+            counts = torch.empty(nc, dtype=torch.int32, device=dev)
+            _lib.check(lib.pnr_raster_count(r, _lib.ptr(counts), st), 'raster_count')
+            ends = torch.cumsum(counts, 0, dtype=torch.int64)
+            pairs = int(ends[-1])
+            nbytes = lib.pnr_raster_workspace_bytes(r, pairs)
+        if nbytes == 0:  # counters or lists past the library's bounds: fewer views per pass
+            if view_batch is not None or b == 1:
+                raise ValueError(f'pnr.recon.render_depth: {b} view(s) of {H} x {W} with {f.shape[0]} faces are out '
+                                 'of range')
+            batch = (b + 1) // 2
+            continue
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.pnr_raster_fill(r, _lib.ptr(counts), _lib.ptr(ends), pairs, _lib.ptr(ws), nbytes, st),
+                   'raster_fill')
+        _lib.check(lib.pnr_raster_tiles(r, _lib.ptr(counts), _lib.ptr(ends), pairs, _lib.ptr(out[i:]), _lib.ptr(ws),
+                                        nbytes, st), 'raster_tiles')
+        i += b
+    return out
+
+
+def depth_l1(a, b):
+    """Per image the mean |a - b| of two (n, H, W) float32 device stacks: (n,) float64, differences and sums in
+    float64 in a fixed order (bitwise reproducible)."""
+    _lib.require_cuda(a, b)
+    if a.dim() != 3 or a.shape != b.shape or a.dtype != torch.float32 or b.dtype != torch.float32 or \
+            a.device != b.device:
+        raise ValueError('pnr.recon.depth_l1: a and b are (n,H,W) float32 tensors of one shape on one device')
+    a, b = a.contiguous(), b.contiguous()
+    n, hw, dev = a.shape[0], a.shape[1] * a.shape[2], a.device
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    if n == 0:
+        return out
+    lib = _lib.load()
+    nbytes = lib.pnr_depth_l1_workspace_bytes(n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.pnr_depth_l1(_lib.ptr(a), _lib.ptr(b), n, hw, _lib.ptr(out), _lib.ptr(ws), nbytes,
+                                _lib.stream_of(dev)), 'depth_l1')
+    return out
+
+
+def _seen(name, points, c2w, H, W, fx, fy, cx, cy, per_view):
+    p = _cloud(name, points)
+    c = _poses(name, c2w, p.device)
+    flags = torch.zeros(c.shape[0] if per_view else p.shape[0], dtype=torch.uint8, device=p.device)
+    if flags.shape[0]:
+        _lib.check(_lib.load().pnr_frustum_seen(_lib.ptr(p), p.shape[0], _lib.ptr(c), c.shape[0], int(H), int(W), fx, fy,
+                                                cx, cy, _lib.ptr(flags) if per_view else None,
+                                                None if per_view else _lib.ptr(flags), _lib.stream_of(p.device)),
+                   'frustum_seen')
+    return flags.bool()
+
+
+def views_seeing(points, c2w, H, W, fx, fy, cx, cy):
+    """(n,) bool: does view i see any of the points, by `check_proj`'s test (include/pnr.h `pnr_frustum_seen`)."""
+    return _seen('views_seeing', points, c2w, H, W, fx, fy, cx, cy, True)
+
+
+def points_seen(points, c2w, H, W, fx, fy, cx, cy):
+    """(P,) bool: does any view see point i, by the same test."""
+    return _seen('points_seen', points, c2w, H, W, fx, fy, cx, cy, False)
+
+
+def cull_mesh(verts, faces, c2w, H=680, W=1200, fx=600., fy=600., cx=599.5, cy=339.5):
+    """src/tools/cull_mesh.py: drop the faces whose three vertices are all seen by none of the (OpenCV) poses.
+    Returns (verts, faces) with the vertices as they came."""
+    v, f = _mesh('cull_mesh', verts, faces)
+    seen = points_seen(v, c2w, H, W, fx, fy, cx, cy)
+    return verts, faces[seen[f].any(1)]
+
+
+def _viewmatrix(z, up, pos):
+    """eval_recon.py `viewmatrix` on (n,3) rows: (n,4,4) camera-to-world poses"""
+    unit = lambda x: x / np.linalg.norm(x, axis=1, keepdims=True)
+    v2 = unit(z)
+    v0 = unit(np.cross(up, v2))
+    v1 = unit(np.cross(v2, v0))
+    c2w = np.tile(np.eye(4), (len(z), 1, 1))
+    c2w[:, :3, :] = np.stack([v0, v1, v2, pos], 2)
+    return c2w
+
+
+def sample_views(gt_verts, n, seed=0, pc_unseen=None, H=500, W=500, focal=300.):
+    """calc_2d_metric's view draw: (n,4,4) float64 poses on the device.  The origin is uniform in the ground
+    truth's axis-aligned bounds about their centre, the smallest extent shrunk to 0.3 and the other two to 0.7
+    (trimesh's oriented bounds are not built), shifted by +0.4 along z; the target is uniform in +-10,000 rounded
+    to 2 decimals, up is (0, 0, -1).  Candidates come from `RandomState(seed)` on the host in blocks; those that
+    see any `pc_unseen` point (`views_seeing`, one call per block) are redrawn."""
+    gv = _cloud('sample_views', gt_verts)
+    lo, hi = gv.min(0).values.cpu().numpy(), gv.max(0).values.cpu().numpy()
+    ext = hi - lo
+    shrink = np.full(3, 0.7)
+    shrink[np.argmin(ext)] = 0.3
+    centre = 0.5 * (lo + hi) + np.array([0.0, 0.0, 0.4])
+    rng = np.random.RandomState(seed)
+    views = np.zeros((0, 4, 4))
+    cxy = (W / 2.0 - 0.5, H / 2.0 - 0.5)
+    for _ in range(1000):
+        if len(views) >= n:
+            break
+        m = max(2 * (n - len(views)), 16)
+        origin = centre + (rng.uniform(size=(m, 3)) - 0.5) * ext * shrink
+        target = np.round(rng.uniform(-10000, 10000, size=(m, 3)), 2)
+        cand = _viewmatrix(target - origin, np.array([0.0, 0.0, -1.0]), origin)
+        if pc_unseen is not None and len(pc_unseen):
+            sees = views_seeing(pc_unseen, torch.from_numpy(cand).to(gv.device), H, W, focal, focal, *cxy)
+            cand = cand[~sees.cpu().numpy()]
+        views = np.concatenate([views, cand])
+    if len(views) < n:
+        raise RuntimeError('pnr.recon.sample_views: no view avoids the unseen points')
+    return torch.from_numpy(views[:n]).to(gv.device)
+
+
+def calc_2d_metric(rec, gt, align=True, n_imgs=1000, pc_unseen=None, seed=0, views=None):
+    """`calc_2d_metric(rec_meshfile, gt_meshfile, align, n_imgs)`, the "Depth L1" column: rec and gt as for
+    `calc_3d_metric`; `pc_unseen` (P,3) are the points no sampled view may see (the reference's
+    `*_pc_unseen.npy`), `views` (n,4,4) OpenCV poses to use instead of `sample_views(gt, n_imgs, seed, pc_unseen)`.
+    Both meshes are rendered at 500 x 500, focal 300, 64 views at a time (the images of a batch are dropped after
+    their L1).  Returns {'depth_l1_cm': mean over the views in cm, 'per_view': (n,) float64 in metres, 'views',
+    'transformation'}."""
+    H = W = 500
+    focal, cx, cy = 300.0, 249.5, 249.5
+    rv, rf = read_ply(rec) if isinstance(rec, str) else rec
+    gv, gf = read_ply(gt) if isinstance(gt, str) else gt
+    rv, rf = _mesh('calc_2d_metric', rv, rf)
+    gv, gf = _mesh('calc_2d_metric', gv, gf)
+    dev = rv.device
+    T = torch.eye(4, dtype=torch.float64, device=dev)
+    if align:
+        T, _, _ = icp(rv, gv, threshold=0.1)
+        rv = transform_points(rv, T)
+    if pc_unseen is not None:
+        pc_unseen = torch.as_tensor(pc_unseen).to(dev)
+    views = sample_views(gv, n_imgs, seed, pc_unseen, H, W, focal) if views is None else _poses('calc_2d_metric', views, dev)
+    per_view = []
+    for i in range(0, views.shape[0], 64):
+        c = views[i:i + 64]
+        per_view.append(depth_l1(render_depth(gv, gf, c, H, W, focal, focal, cx, cy),
+                                 render_depth(rv, rf, c, H, W, focal, focal, cx, cy)))
+    per_view = torch.cat(per_view) if per_view else torch.zeros(0, dtype=torch.float64, device=dev)
+    return {'depth_l1_cm': float(per_view.mean()) * 100.0 if len(per_view) else 0.0, 'per_view': per_view,
+            'views': views, 'transformation': T}
