@@ -654,7 +654,37 @@ int pnr_bound_contains_f64(const double* p, int64_t P, const double* planes, int
  * points to *n_points (device) and leaves the offsets in the workspace for _emit; xyz, rgb (n_points,3)
  * float32, rgb may be NULL (and must be when the volume keeps no colour).
  * ws: pnr_tsdf_workspace_bytes() bytes (0 for bad arguments), 4-byte aligned, any contents.  Bad arguments:
- * PNR_E_ARG; a short workspace: PNR_E_WORKSPACE; nothing is launched. */
+ * PNR_E_ARG; a short workspace: PNR_E_WORKSPACE; nothing is launched.
+ *
+ * pnr_tsdf_mesh_count / _emit give the volume's coloured triangle mesh: marching cubes at level 0, slot by
+ * slot over the blocks, neighbour blocks found through the directory.
+ *   corner     a voxel of a live block (entry >= 0) with w > 0 is valid; its sample is its tsdf, and it is
+ *              below when tsdf < 0 (pnr_marching_cubes' rule with level 0).
+ *   cell       belongs to the voxel (i, j, k) of slot s at its lowest corner; the other seven corners are at
+ *              +1 along the axes, in the same block or in one of the seven +x/+y/+z neighbour blocks.  A cell
+ *              is valid when all eight corners are: a cell that touches an absent or dropped block, the edge of
+ *              the directory or a w == 0 voxel emits nothing (open3d's rule).  Case index and triangles are
+ *              pnr_marching_cubes' (corner c = (c & 1, c >> 1 & 1, c >> 2) sets bit c; the same edge numbers).
+ *   vertex     an edge belongs to the voxel at its lower end and has an axis a.  It carries a vertex when
+ *              exactly one end is below and at least one of the up to four cells around it is valid, so every
+ *              vertex is referenced.  s = tsdf0 / (tsdf0 - tsdf1), xyz = X0, xyz_a = X0_a + voxel_length s,
+ *              rgb_c = rgb0_c + (rgb1_c - rgb0_c) s in unfused float32: a vertex whose edge has
+ *              tsdf0 tsdf1 < 0 is bit for bit a point of pnr_tsdf_extract_emit.  The faces around a vertex
+ *              share it, across block faces too.
+ *   order      vertices by (slot, voxel index, axis), faces by (slot, voxel index of the cell, case-table
+ *              order).  No atomic decides a position: equal volumes give equal bits.
+ *   winding    the table's, unchanged: with below = tsdf < 0 the normal (v1 - v0) x (v2 - v0) points towards
+ *              positive tsdf, the free space in front of the surface.
+ * _count writes V and F to *n_vertices, *n_faces (device) and leaves in the workspace what _emit needs; xyz,
+ * rgb (V,3) float32, rgb may be NULL (and must be when the volume keeps no colour), faces (F,3) int32.
+ * V, F < 2^31: a volume whose max_blocks 4096 5 faces would not fit (max_blocks > 104,857) has a workspace
+ * size of 0 and is refused with PNR_E_ARG by both calls, since the counts are known on the device only.
+ * ws: pnr_tsdf_mesh_workspace_bytes() bytes, 8-byte aligned, any contents before _count.  After it: int32
+ * vertex and face totals per slot (2 max_blocks), their exclusive scans (2 (max_blocks + 1)), the scan's
+ * scratch, and per slot 256 uint64 rank rows, row (k, j): bits 0-15, 16-31, 32-47 mark the voxels i whose
+ * x, y, z edge carries a vertex, bits 48-63 count the slot's vertices before the row.  A vertex index is the
+ * owning slot's scanned offset + the row's count + the marks before (i, a) in (voxel, axis) order.
+ * Bad arguments: PNR_E_ARG; a short workspace: PNR_E_WORKSPACE; nothing is launched. */
 typedef struct pnr_tsdf {
   float origin[3];
   float voxel_length, sdf_trunc, depth_trunc;
@@ -676,6 +706,11 @@ int pnr_tsdf_integrate(const pnr_tsdf* vol, const float* depth, const float* col
                        void* ws, size_t ws_bytes, void* stream);
 int pnr_tsdf_extract_count(const pnr_tsdf* vol, void* ws, size_t ws_bytes, int64_t* n_points, void* stream);
 int pnr_tsdf_extract_emit(const pnr_tsdf* vol, const void* ws, size_t ws_bytes, float* xyz, float* rgb, void* stream);
+size_t pnr_tsdf_mesh_workspace_bytes(const pnr_tsdf* vol);
+int pnr_tsdf_mesh_count(const pnr_tsdf* vol, void* ws, size_t ws_bytes, int64_t* n_vertices, int64_t* n_faces,
+                        void* stream);
+int pnr_tsdf_mesh_emit(const pnr_tsdf* vol, const void* ws, size_t ws_bytes, float* xyz, float* rgb, int32_t* faces,
+                       void* stream);
 
 /* ---- two-way descriptor matching (src/Tracker.py:398-440, nn_match_two_way; additions to ABI 14) ----
  * desc1 (D,N), desc2 (D,M): float32 row-major with unit-norm columns (the reference's SuperPoint layout);

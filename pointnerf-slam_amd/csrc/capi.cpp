@@ -98,6 +98,9 @@ int launch_tsdf_reset(const pnr_tsdf*, hipStream_t);
 int launch_tsdf_integrate(const pnr_tsdf*, const float*, const float*, const float*, int32_t, void*, size_t, hipStream_t);
 int launch_tsdf_extract_count(const pnr_tsdf*, void*, size_t, int64_t*, hipStream_t);
 int launch_tsdf_extract_emit(const pnr_tsdf*, const void*, size_t, float*, float*, hipStream_t);
+size_t tsdf_mesh_workspace_bytes(const pnr_tsdf*);
+int launch_tsdf_mesh_count(const pnr_tsdf*, void*, size_t, int64_t*, int64_t*, hipStream_t);
+int launch_tsdf_mesh_emit(const pnr_tsdf*, const void*, size_t, float*, float*, int32_t*, hipStream_t);
 size_t match_workspace_bytes(int64_t, int64_t);
 int launch_match_two_way(const float*, const float*, int32_t, int64_t, int64_t, float, int32_t*, int32_t*, float*,
                          int32_t*, void*, size_t, hipStream_t);
@@ -1688,6 +1691,18 @@ int pnr_tsdf_extract_count(const pnr_tsdf* vol, void* ws, size_t ws_bytes, int64
 
 int pnr_tsdf_extract_emit(const pnr_tsdf* vol, const void* ws, size_t ws_bytes, float* xyz, float* rgb, void* stream) {
   return launch_tsdf_extract_emit(vol, ws, ws_bytes, xyz, rgb, (hipStream_t)stream);
+}
+
+size_t pnr_tsdf_mesh_workspace_bytes(const pnr_tsdf* vol) { return tsdf_mesh_workspace_bytes(vol); }
+
+int pnr_tsdf_mesh_count(const pnr_tsdf* vol, void* ws, size_t ws_bytes, int64_t* n_vertices, int64_t* n_faces,
+                        void* stream) {
+  return launch_tsdf_mesh_count(vol, ws, ws_bytes, n_vertices, n_faces, (hipStream_t)stream);
+}
+
+int pnr_tsdf_mesh_emit(const pnr_tsdf* vol, const void* ws, size_t ws_bytes, float* xyz, float* rgb, int32_t* faces,
+                       void* stream) {
+  return launch_tsdf_mesh_emit(vol, ws, ws_bytes, xyz, rgb, faces, (hipStream_t)stream);
 }
 
 // ---- two-way descriptor matching (match.hip; Tracker.py:398-440) --------------------------------------

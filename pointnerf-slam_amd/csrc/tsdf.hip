@@ -20,10 +20,14 @@
 //   k_tsdf_extract    count and emit in one template: a wave covers 64 consecutive voxel indices of a row,
 //                     three ballots per row give the wave's count (count) or a lane's offset inside the
 //                     wave (emit); the scan runs over (slot, row, wave) counts.
+//   k_tsdf_mesh       marching cubes slot by slot, count and emit in one template (described at the kernel):
+//                     an 18^3 halo tile per block in LDS, ballot prefix sums, and per slot 256 rank rows in the
+//                     workspace through which a face finds a vertex that a neighbour block owns.
 // Integer atomics only; vector stores only.
 #include <float.h>
 #include <limits.h>
 
+#include "mc_table.h"
 #include "pnr_internal.h"
 #include "points_hash.h"
 #include "window_sample.h"
@@ -383,6 +387,252 @@ __global__ __launch_bounds__(256) void k_tsdf_extract(TsdfArgs a, int32_t* __res
 
 __global__ void k_tsdf_total(const int32_t* __restrict__ offs, int64_t n, int64_t* __restrict__ out) { out[0] = offs[n]; }
 
+// ---- triangle mesh (pnr_tsdf_mesh_count / _emit) ---------------------------------------------------------
+// One template for both calls, a workgroup per live slot.  The slot's 18^3 halo tile (voxels -1..16 per axis;
+// tile index (z 18 + y) 18 + x of voxel (x - 1, y - 1, z - 1)) is staged through the 27 directory entries
+// around the block: a flag byte per voxel (bit 0 valid, bit 1 below) and, for the emit, the tsdf value.  A
+// second sweep marks the 17^3 cells of the tile whose eight corners are valid, so the voxel pass decides from
+// LDS alone which owned edges carry a vertex (one of the four cells around the edge is valid) and the cell's
+// case.  Thread t = j 16 + i walks its column in z as the other kernels here do; a wave covers 64 consecutive
+// voxel indices, ballots of the edge bits and of the triangle count's three bits give the wave's totals and
+// every lane's offset, and wave 0 scans the 64 (z, wave) totals of the block.  The count writes the block's
+// totals and its rank rows; the emit rebuilds the same offsets, keeps its own rank rows in LDS and reads a
+// neighbour's from the workspace.
+constexpr int kTile = kBlk + 2;
+constexpr int kTileN = kTile * kTile * kTile;
+constexpr int kTy = kTile, kTz = kTile * kTile;  // tile strides
+constexpr int kRankRows = kBlk * kBlk;           // rows (k, j) of a slot
+constexpr int kUnits = kBlk * 4;                 // (z, wave) units of a slot
+
+// workspace of the mesh calls: vcnt[max_blocks] | fcnt[max_blocks] | voff[max_blocks + 1] | foff[max_blocks + 1]
+// | scan scratch | rank[max_blocks][256] uint64.  A rank row (k, j) of a slot: bits 0-15, 16-31, 32-47 the
+// voxels i of the row whose x, y, z edge carries a vertex, bits 48-63 the slot's vertices before the row.
+struct MeshWs {
+  int32_t *vcnt, *fcnt, *voff, *foff, *scratch;
+  unsigned long long* rank;
+};
+static size_t mesh_ws_layout(void* base, int32_t max_blocks, MeshWs* w) {
+  char* b = static_cast<char*>(base);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* p = b ? b + off : nullptr;
+    off += a256(bytes);
+    return p;
+  };
+  MeshWs v;
+  v.vcnt = reinterpret_cast<int32_t*>(take((size_t)max_blocks * 4));
+  v.fcnt = reinterpret_cast<int32_t*>(take((size_t)max_blocks * 4));
+  v.voff = reinterpret_cast<int32_t*>(take((size_t)(max_blocks + 1) * 4));
+  v.foff = reinterpret_cast<int32_t*>(take((size_t)(max_blocks + 1) * 4));
+  v.scratch = reinterpret_cast<int32_t*>(take((size_t)scan_scratch_ints(max_blocks) * 4));
+  v.rank = reinterpret_cast<unsigned long long*>(take((size_t)max_blocks * kRankRows * 8));
+  if (w) *w = v;
+  return off;
+}
+
+struct MeshOut {
+  float* xyz;
+  float* rgb;
+  int32_t* faces;
+};
+
+// The vertices of a slot before the one on edge `ax` of voxel xi of a rank row (order: voxel, then axis).
+__device__ __forceinline__ int rank_in_slot(unsigned long long row, int xi, int ax) {
+  const unsigned long long lo = (1ull << xi) - 1ull, le = (2ull << xi) - 1ull;
+  const unsigned long long sel = (ax > 0 ? le : lo) | ((ax > 1 ? le : lo) << 16) | (lo << 32);
+  return (int)(row >> 48) + __popcll(row & sel);
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_tsdf_mesh(TsdfArgs a, MeshWs m, MeshOut o) {
+  PNR_FP_STRICT
+  __shared__ float s_t[EMIT ? kTileN : 1];
+  // flags and cells; the emit writes the voxel words over them once the voxel pass has read them
+  __shared__ __attribute__((aligned(16))) unsigned char s_buf[EMIT ? kVox * 4 : 2 * kTileN];
+  static_assert(2 * kTileN <= kVox * 4, "the words cover the flags and the cells");
+  unsigned char* const s_flag = s_buf;
+  unsigned char* const s_cell = s_buf + kTileN;
+  uint32_t* const s_word = reinterpret_cast<uint32_t*>(s_buf);
+  __shared__ unsigned long long s_rank[EMIT ? kRankRows : 1];
+  __shared__ int s_nb[27], s_uv[kUnits], s_uf[kUnits], s_tot[2];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int ix = t & (kBlk - 1), iy = t >> 4;
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const int n_blocks = a.hdr[0];
+  const int n_slots = EMIT ? n_blocks : a.max_blocks;  // the count zeroes the totals of the unused slots too
+  for (int slot = blockIdx.x; slot < n_slots; slot += gridDim.x) {
+    if (slot >= n_blocks) {
+      if (t == 0) m.vcnt[slot] = m.fcnt[slot] = 0;
+      continue;
+    }
+    const int e = a.block_index[slot];
+    const int bx = e % a.nx, by = (e / a.nx) % a.ny, bz = e / (a.nx * a.ny);
+    __syncthreads();  // the previous slot's tile is no longer read
+    if (t < 27) {
+      const int cx = bx + t % 3 - 1, cy = by + (t / 3) % 3 - 1, cz = bz + t / 9 - 1;
+      int s1 = -1;
+      if (cx >= 0 && cx < a.nx && cy >= 0 && cy < a.ny && cz >= 0 && cz < a.nz)
+        s1 = a.dir[((int64_t)cz * a.ny + cy) * a.nx + cx];
+      s_nb[t] = s1 < 0 ? -1 : s1;
+    }
+    __syncthreads();
+    for (int q = t; q < kTileN; q += 256) {
+      const int x = q % kTile, y = (q / kTile) % kTile, z = q / kTz;
+      // x = 0 lies in the block before, 1..16 in this one, 17 in the next: (x + 15) >> 4 = 0, 1, 2
+      const int s1 = s_nb[(((z + 15) >> 4) * 3 + ((y + 15) >> 4)) * 3 + ((x + 15) >> 4)];
+      unsigned char flag = 0;
+      float tv = 0.f;
+      if (s1 >= 0) {
+        const int64_t at = (int64_t)s1 * kVox + ((((z + 15) & 15) * kBlk + ((y + 15) & 15)) * kBlk + ((x + 15) & 15));
+        if (a.weight[at] > 0.f) {
+          tv = a.tsdf[at];
+          flag = tv < 0.f ? 3 : 1;
+        }
+      }
+      s_flag[q] = flag;
+      if (EMIT) s_t[q] = tv;
+    }
+    __syncthreads();
+    for (int q = t; q < kTileN; q += 256) {
+      const int x = q % kTile, y = (q / kTile) % kTile, z = q / kTz;
+      unsigned char c = 0;
+      if (x < kTile - 1 && y < kTile - 1 && z < kTile - 1)
+        c = s_flag[q] & s_flag[q + 1] & s_flag[q + kTy] & s_flag[q + kTy + 1] & s_flag[q + kTz] &
+            s_flag[q + kTz + 1] & s_flag[q + kTz + kTy] & s_flag[q + kTz + kTy + 1] & 1;
+      s_cell[q] = c;
+    }
+    __syncthreads();
+    // per voxel: bits 0-2 owned edges with a vertex, 3-10 the case of its cell (0 when the cell is not valid),
+    // 11-18 the vertices and 19-27 the faces of the lanes before it in the wave (<= 63 3, <= 63 MC_MAX_TRI)
+    static_assert(63 * 3 < (1 << 8) && 63 * MC_MAX_TRI < (1 << 9) && (kVox - 1) * 3 < (1 << 16), "packed fields");
+    uint32_t word[kBlk];
+#pragma unroll
+    for (int z = 0; z < kBlk; ++z) {
+      const int q0 = ((z + 1) * kTile + (iy + 1)) * kTile + (ix + 1);
+      const uint32_t f0 = s_flag[q0], fx = s_flag[q0 + 1], fy = s_flag[q0 + kTy], fz = s_flag[q0 + kTz];
+      const uint32_t c0 = s_cell[q0], cmx = s_cell[q0 - 1], cmy = s_cell[q0 - kTy], cmz = s_cell[q0 - kTz];
+      const uint32_t around_x = c0 | cmy | cmz | s_cell[q0 - kTy - kTz];
+      const uint32_t around_y = c0 | cmx | cmz | s_cell[q0 - 1 - kTz];
+      const uint32_t around_z = c0 | cmx | cmy | s_cell[q0 - 1 - kTy];
+      const uint32_t em = (((f0 ^ fx) >> 1) & around_x) | ((((f0 ^ fy) >> 1) & around_y) << 1) |
+                          ((((f0 ^ fz) >> 1) & around_z) << 2);
+      uint32_t cs = 0;
+      if (c0)
+        cs = (f0 >> 1) | ((fx >> 1) << 1) | ((fy >> 1) << 2) | ((uint32_t)(s_flag[q0 + kTy + 1] >> 1) << 3) |
+             ((fz >> 1) << 4) | ((uint32_t)(s_flag[q0 + kTz + 1] >> 1) << 5) |
+             ((uint32_t)(s_flag[q0 + kTz + kTy] >> 1) << 6) | ((uint32_t)(s_flag[q0 + kTz + kTy + 1] >> 1) << 7);
+      const uint32_t nt = MC_NTRI[cs];
+      const unsigned long long v0 = __ballot(em & 1), v1 = __ballot(em & 2), v2 = __ballot(em & 4);
+      const unsigned long long t0 = __ballot(nt & 1), t1 = __ballot(nt & 2), t2 = __ballot(nt & 4);
+      const uint32_t pv = __popcll(v0 & lt) + __popcll(v1 & lt) + __popcll(v2 & lt);
+      const uint32_t pf = __popcll(t0 & lt) + 2 * __popcll(t1 & lt) + 4 * __popcll(t2 & lt);
+      if (lane == 0) {
+        s_uv[z * 4 + wave] = __popcll(v0) + __popcll(v1) + __popcll(v2);
+        s_uf[z * 4 + wave] = __popcll(t0) + 2 * __popcll(t1) + 4 * __popcll(t2);
+      }
+      word[z] = em | (cs << 3) | (pv << 11) | (pf << 19);
+    }
+    __syncthreads();
+    if (wave == 0) {  // exclusive scan of the 64 unit totals, in (z, wave) order
+      const int cv = s_uv[lane], cf = s_uf[lane];
+      int sv = cv, sf = cf;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const int uv = __shfl_up(sv, d), uf = __shfl_up(sf, d);
+        if (lane >= d) {
+          sv += uv;
+          sf += uf;
+        }
+      }
+      s_uv[lane] = sv - cv;
+      s_uf[lane] = sf - cf;
+      if (lane == 63) {
+        s_tot[0] = sv;
+        s_tot[1] = sf;
+      }
+    }
+    __syncthreads();
+    if (!EMIT && t == 0) {
+      m.vcnt[slot] = s_tot[0];
+      m.fcnt[slot] = s_tot[1];
+    }
+    unsigned long long* rows = EMIT ? s_rank : m.rank + (int64_t)slot * kRankRows;
+#pragma unroll
+    for (int z = 0; z < kBlk; ++z) {
+      const uint32_t em = word[z] & 7u;
+      const unsigned long long v0 = __ballot(em & 1), v1 = __ballot(em & 2), v2 = __ballot(em & 4);
+      if (ix == 0) {  // the first lane of each of the wave's four rows
+        const int sh = lane & 48;
+        const unsigned long long before = (1ull << sh) - 1ull;
+        const unsigned long long pre =
+            (unsigned long long)(s_uv[z * 4 + wave] + __popcll(v0 & before) + __popcll(v1 & before) + __popcll(v2 & before));
+        rows[z * kBlk + iy] = (pre << 48) | ((v0 >> sh) & 0xffffull) | (((v1 >> sh) & 0xffffull) << 16) |
+                              (((v2 >> sh) & 0xffffull) << 32);
+      }
+    }
+    if (!EMIT) continue;
+#pragma unroll
+    for (int z = 0; z < kBlk; ++z) s_word[z * 256 + t] = word[z];  // (every flag and cell was read two barriers ago)
+    __syncthreads();  // the rank rows and the words of this slot are in LDS
+    const int64_t vbase = m.voff[slot], fbase = m.foff[slot];
+    const float X0 = voxel_centre(a.o0, bx * kBlk + ix, a.vl), X1 = voxel_centre(a.o1, by * kBlk + iy, a.vl);
+    for (int z = 0; z < kBlk; ++z) {
+      const uint32_t w = s_word[z * 256 + t], em = w & 7u, cs = (w >> 3) & 255u;
+      const int unit = z * 4 + wave;
+      if (em) {
+        const int q0 = ((z + 1) * kTile + (iy + 1)) * kTile + (ix + 1);
+        const float X[3] = {X0, X1, voxel_centre(a.o2, bz * kBlk + z, a.vl)};
+        const float t0 = s_t[q0];
+        int64_t pos = vbase + s_uv[unit] + (int)((w >> 11) & 255u);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          if (!(em & (1u << c))) continue;
+          const float s = t0 / (t0 - s_t[q0 + (c == 0 ? 1 : (c == 1 ? kTy : kTz))]);
+#pragma unroll
+          for (int k = 0; k < 3; ++k) o.xyz[pos * 3 + k] = k == c ? X[k] + a.vl * s : X[k];
+          if (o.rgb) {
+            const int x1 = ix + (c == 0), y1 = iy + (c == 1), z1 = z + (c == 2);
+            const int64_t s1 = s_nb[(((z1 >> 4) + 1) * 3 + ((y1 >> 4) + 1)) * 3 + ((x1 >> 4) + 1)];
+            const int v1i = ((z1 & 15) * kBlk + (y1 & 15)) * kBlk + (x1 & 15);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+              const float c0 = a.rgb[((int64_t)slot * 3 + k) * kVox + z * 256 + t];
+              const float c1 = a.rgb[(s1 * 3 + k) * kVox + v1i];
+              o.rgb[pos * 3 + k] = c0 + (c1 - c0) * s;
+            }
+          }
+          ++pos;
+        }
+      }
+      const int nt = MC_NTRI[cs];
+      int64_t f = fbase + s_uf[unit] + (int)((w >> 19) & 511u);
+      for (int k = 0; k < nt; ++k, ++f) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const int ed = MC_TRI[cs][3 * k + j];
+          const int ax = ed >> 2, db = ed & 1, dc = (ed >> 1) & 1;
+          // the two other axes in increasing order carry (db, dc), as in mesh.hip
+          const int x1 = ix + (ax == 0 ? 0 : db), y1 = iy + (ax == 1 ? 0 : (ax == 0 ? db : dc)),
+                    z1 = z + (ax == 2 ? 0 : dc);
+          const int nb = (((z1 >> 4) + 1) * 3 + ((y1 >> 4) + 1)) * 3 + ((x1 >> 4) + 1);
+          const int row = (z1 & 15) * kBlk + (y1 & 15);
+          // a valid cell's corners are voxels of live blocks: s_nb[nb] >= 0
+          const int s1 = s_nb[nb];
+          const unsigned long long r = nb == 13 ? s_rank[row] : m.rank[(int64_t)s1 * kRankRows + row];
+          const int32_t base = nb == 13 ? (int32_t)vbase : m.voff[s1];
+          o.faces[f * 3 + j] = base + rank_in_slot(r, x1 & 15, ax);
+        }
+      }
+    }
+  }
+}
+
+__global__ void k_tsdf_mesh_total(const int32_t* __restrict__ voff, const int32_t* __restrict__ foff, int64_t n,
+                                  int64_t* __restrict__ n_v, int64_t* __restrict__ n_f) {
+  n_v[0] = voff[n];
+  n_f[0] = foff[n];
+}
+
 }  // namespace
 
 size_t tsdf_directory_bytes(const pnr_tsdf* v) {
@@ -465,6 +715,50 @@ int launch_tsdf_extract_emit(const pnr_tsdf* v, const void* ws, size_t ws_bytes,
   const int cus = device_cu_count();
   const int grid = a.max_blocks < 8 * cus ? a.max_blocks : 8 * cus;
   hipLaunchKernelGGL(k_tsdf_extract<true>, dim3((unsigned)grid), dim3(256), 0, st, a, nullptr, w.offs, xyz, rgb);
+  return hip_status(hipGetLastError());
+}
+
+// A volume can be meshed when max_blocks cells' worth of faces fits an int32 whatever the surface (3 vertices
+// per voxel always do): the counts come back on the device, so the limit is checked on the size.
+static bool mesh_args(const pnr_tsdf* v, TsdfArgs& a, bool need_buffers) {
+  return tsdf_args(v, a, need_buffers) && (int64_t)a.max_blocks * kVox * MC_MAX_TRI <= (int64_t)INT_MAX;
+}
+
+size_t tsdf_mesh_workspace_bytes(const pnr_tsdf* v) {
+  TsdfArgs a;
+  if (!mesh_args(v, a, false)) return 0;
+  return mesh_ws_layout(nullptr, a.max_blocks, nullptr);
+}
+
+int launch_tsdf_mesh_count(const pnr_tsdf* v, void* ws, size_t ws_bytes, int64_t* n_vertices, int64_t* n_faces,
+                           hipStream_t st) {
+  TsdfArgs a;
+  if (!mesh_args(v, a, true) || !n_vertices || !n_faces || ((uintptr_t)ws & 7)) return PNR_E_ARG;
+  if (!ws || ws_bytes < tsdf_mesh_workspace_bytes(v)) return PNR_E_WORKSPACE;
+  MeshWs w;
+  mesh_ws_layout(ws, a.max_blocks, &w);
+  const int cus = device_cu_count();
+  const int grid = a.max_blocks < 8 * cus ? a.max_blocks : 8 * cus;
+  hipLaunchKernelGGL(k_tsdf_mesh<false>, dim3((unsigned)grid), dim3(256), 0, st, a, w, MeshOut{nullptr, nullptr, nullptr});
+  int rc = scan_exclusive(w.vcnt, w.voff, a.max_blocks, w.scratch, st);
+  if (rc) return rc;
+  rc = scan_exclusive(w.fcnt, w.foff, a.max_blocks, w.scratch, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_tsdf_mesh_total, dim3(1), dim3(1), 0, st, w.voff, w.foff, (int64_t)a.max_blocks, n_vertices,
+                     n_faces);
+  return hip_status(hipGetLastError());
+}
+
+int launch_tsdf_mesh_emit(const pnr_tsdf* v, const void* ws, size_t ws_bytes, float* xyz, float* rgb, int32_t* faces,
+                          hipStream_t st) {
+  TsdfArgs a;
+  if (!mesh_args(v, a, true) || !xyz || !faces || (rgb && !a.rgb) || ((uintptr_t)ws & 7)) return PNR_E_ARG;
+  if (!ws || ws_bytes < tsdf_mesh_workspace_bytes(v)) return PNR_E_WORKSPACE;
+  MeshWs w;
+  mesh_ws_layout(const_cast<void*>(ws), a.max_blocks, &w);
+  const int cus = device_cu_count();
+  const int grid = a.max_blocks < 8 * cus ? a.max_blocks : 8 * cus;
+  hipLaunchKernelGGL(k_tsdf_mesh<true>, dim3((unsigned)grid), dim3(256), 0, st, a, w, MeshOut{xyz, rgb, faces});
   return hip_status(hipGetLastError());
 }
 

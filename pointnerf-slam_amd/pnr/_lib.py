@@ -256,6 +256,9 @@ _SIGS = {
     'pnr_tsdf_integrate': (ctypes.c_int, [PTsdf, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
     'pnr_tsdf_extract_count': (ctypes.c_int, [PTsdf, c_void_p, c_size_t, c_void_p, c_void_p]),
     'pnr_tsdf_extract_emit': (ctypes.c_int, [PTsdf, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    'pnr_tsdf_mesh_workspace_bytes': (c_size_t, [PTsdf]),
+    'pnr_tsdf_mesh_count': (ctypes.c_int, [PTsdf, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    'pnr_tsdf_mesh_emit': (ctypes.c_int, [PTsdf, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     'pnr_match_workspace_bytes': (c_size_t, [c_int64, c_int64]),
     'pnr_match_two_way': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int64, c_float, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

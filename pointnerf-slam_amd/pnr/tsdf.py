@@ -4,7 +4,7 @@ ScalableTSDFVolume.integrate per keyframe) and the usual way a neural-point SLAM
 
 Blocks of 16^3 voxels behind a dense directory over `bound` padded by `sdf_trunc`; the slot arrays hold
 `max_blocks` blocks.  Nothing here reads the device except the two counters (`n_blocks`, `dropped_blocks`) and
-the point count of `extract_points`, as marching cubes reads its counts.
+the counts of `extract_points` and `extract_triangle_mesh`, as marching cubes reads its counts.
 """
 from __future__ import annotations
 
@@ -54,6 +54,7 @@ class TSDFVolume(object):
         self.block_index = torch.empty(self.max_blocks, dtype=torch.int32, device=self.device)
         _lib.require_cuda(self.directory)
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
+        self.mesh_ws = None   # allocated by the first extract_triangle_mesh
         v.directory, v.tsdf, v.weight = self.directory.data_ptr(), self.tsdf.data_ptr(), self.weight.data_ptr()
         v.rgb = self.rgb.data_ptr() if color else None
         v.block_index = self.block_index.data_ptr()
@@ -113,6 +114,29 @@ class TSDFVolume(object):
             _lib.check(self.lib.pnr_tsdf_extract_emit(self._ref(), _lib.ptr(self.ws), self.ws_bytes, _lib.ptr(xyz),
                                                       _lib.ptr(rgb), st), 'tsdf_extract_emit')
         return xyz, (rgb if rgb is not None else torch.zeros_like(xyz))
+
+    def extract_triangle_mesh(self):
+        """(verts (V,3) float32, faces (F,3) int32, rgb (V,3) float32) on the device: marching cubes over the
+        blocks, the cells that touch unobserved space left out, vertices shared across block faces and ordered
+        by (slot, voxel index, axis) (include/pnr.h `pnr_tsdf_mesh_count`).  rgb is zeros for a volume without
+        colour.  The two counts are the only host reads."""
+        if self.mesh_ws is None:
+            nbytes = self.lib.pnr_tsdf_mesh_workspace_bytes(self._ref())
+            if nbytes == 0:
+                raise ValueError('pnr.tsdf: max_blocks 4096 5 faces do not fit an int32 index')
+            self.mesh_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        st, ws = _lib.stream_of(self.device), self.mesh_ws
+        counts = torch.zeros(2, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.pnr_tsdf_mesh_count(self._ref(), _lib.ptr(ws), ws.numel(), _lib.ptr(counts),
+                                                _lib.ptr(counts[1:]), st), 'tsdf_mesh_count')
+        n_v, n_f = (int(x) for x in counts.tolist())
+        verts = torch.empty((n_v, 3), dtype=torch.float32, device=self.device)
+        faces = torch.empty((n_f, 3), dtype=torch.int32, device=self.device)
+        rgb = torch.empty((n_v, 3), dtype=torch.float32, device=self.device) if self.rgb is not None else None
+        if n_v > 0:
+            _lib.check(self.lib.pnr_tsdf_mesh_emit(self._ref(), _lib.ptr(ws), ws.numel(), _lib.ptr(verts),
+                                                   _lib.ptr(rgb), _lib.ptr(faces), st), 'tsdf_mesh_emit')
+        return verts, faces, (rgb if rgb is not None else torch.zeros_like(verts))
 
     @property
     def n_blocks(self):

@@ -1,6 +1,6 @@
 """Fusing keyframe depth into the block-sparse TSDF volume (pnr.TSDFVolume, csrc/tsdf.hip) on one MI355X.
 
-  python tools/tsdf_bench.py [--iters K] [--out profiles/tsdf.json]
+  python tools/tsdf_bench.py [--iters K] [--out profiles/tsdf.json] [--mesh-out profiles/tsdf_mesh.json]
 
 Eight synthetic 680x1200 keyframes as tools/mesh_eval_bench.py makes them (the scene pose yawed round the
 circle, depth 0.3 + 0.3 rand), fused over the scene bound at the reference's settings (voxel 4 scale / 512,
@@ -11,6 +11,8 @@ runs after one warm-up, each on a volume reset before the run:
   integrate_8    one call over the eight frames (an empty volume: allocate + integrate)
   integrate_1x8  eight single-frame calls
   extract        extract_points (count, scan, its host read, emit)
+  mesh           extract_triangle_mesh (count, two scans, its host read, emit), to --mesh-out; the count and the
+                 emit calls also apart, between device events
 Algorithmic bytes of a call: 20 B read + 20 B written per voxel of an allocated block (tsdf, weight, rgb) and
 4 B per valid depth pixel.  Reported against the 8 TB/s HBM peak; no target was set: a first measurement.
 """
@@ -53,6 +55,7 @@ def main():
     ap.add_argument('--iters', type=int, default=5)
     ap.add_argument('--max-blocks', type=int, default=16384)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'tsdf.json'))
+    ap.add_argument('--mesh-out', default=os.path.join(REPO, 'profiles', 'tsdf_mesh.json'))
     args = ap.parse_args()
     import pnr
     dev = torch.device('cuda:0')
@@ -92,11 +95,50 @@ def main():
         'integrate_8_hbm_fraction': call_bytes / (t_again * 1e-3) / HBM_BYTES_PER_S,
         'integrate_1x8_bytes': K * n_blocks * 4096 * 40 + valid * 4,
     }
-    print(json.dumps(res))
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(res, f, indent=1)
-        f.write('\n')
+    mesh = mesh_leg(vol, args.iters)
+    mesh.update(frames=[K, H, W], blocks=n_blocks, max_blocks=args.max_blocks, iters=args.iters)
+    for path, r in ((args.out, res), (args.mesh_out, mesh)):
+        print(json.dumps(r))
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, 'w') as f:
+            json.dump(r, f, indent=1)
+            f.write('\n')
+
+
+def mesh_leg(vol, iters):
+    """extract_triangle_mesh on the fused volume: the whole call as wall time, and the two C calls between
+    device events (count: k_tsdf_mesh<count>, two scans, the totals; emit: k_tsdf_mesh<emit>)."""
+    from pnr import _lib
+    t_wall = median_ms(vol.extract_triangle_mesh, iters)
+    verts, faces, _ = vol.extract_triangle_mesh()
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    rgb = torch.empty_like(verts)
+    counts = torch.zeros(2, dtype=torch.int64, device=vol.device)
+    st, ws = _lib.stream_of(vol.device), vol.mesh_ws
+    calls = {
+        'count': lambda: vol.lib.pnr_tsdf_mesh_count(vol._ref(), _lib.ptr(ws), ws.numel(), _lib.ptr(counts),
+                                                     _lib.ptr(counts[1:]), st),
+        'emit': lambda: vol.lib.pnr_tsdf_mesh_emit(vol._ref(), _lib.ptr(ws), ws.numel(), _lib.ptr(verts), _lib.ptr(rgb),
+                                                   _lib.ptr(faces), st),
+    }
+    ms = {'extract_triangle_mesh': t_wall}
+    for name, call in calls.items():
+        out = []
+        for i in range(iters + 1):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            _lib.check(call(), 'tsdf_mesh_' + name)
+            ev[1].record()
+            torch.cuda.synchronize()
+            out.append(ev[0].elapsed_time(ev[1]))
+        ms[name + '_device'] = statistics.median(out[1:])
+    assert counts.tolist() == [V, F]
+    # each pass reads tsdf and weight of every live voxel once (the halo's second reads hit the cache and are not
+    # counted); the count writes the rank rows, the emit reads two colours and writes xyz, rgb per vertex and a face
+    n = vol.n_blocks
+    nbytes = {'count': n * 4096 * 8 + n * 256 * 8, 'emit': n * 4096 * 8 + V * (24 + 24) + F * 12}
+    return {'vertices': V, 'faces': F, 'ms': ms, 'algorithmic_bytes': nbytes,
+            'hbm_fraction': {k: nbytes[k] / (ms[k + '_device'] * 1e-3) / HBM_BYTES_PER_S for k in nbytes}}
 
 
 if __name__ == '__main__':
